@@ -1,6 +1,7 @@
 """Benchmark of the MI355X path_mis hot path (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2] [--mode wavefront] [--scaling weak|strong]
+                    [--dump-outputs DIR] [--full]
 
 Workload (N=1, BASELINE.json configs[1]): Cornell box diffuse-only (C2: both spheres
 diffuse), 1024x1024, 256 spp, path_mis, per-path pcg32 seeding. One step = `--rounds`
@@ -17,7 +18,12 @@ time over ranks. --scaling weak (default): a step is N x --rounds sample rounds 
 strong: a fixed image (C4, 2048^2, --rounds x --steps spp) split over the ranks by blocks.
 `value` = all ranks' samples / the max-over-ranks time.
 
-The JSON line also carries:
+A plain run does what the headline figure needs and nothing else: scene setup, --warmup steps, the --steps timed
+steps, then the JSON line (`value`, `ms_per_step` = the milliseconds one timed step took). --dump-outputs DIR writes
+what the timed steps computed, the RGBW framebuffer a caller reads back after the last step (rank 0's reduced one at
+N > 1), as DIR/framebuffer.npy; scene and seeds are fixed by the arguments, so two builds compare output for output.
+
+With --full the run also measures the records below, and the JSON line carries them (null in a plain run):
   roofline      the dominant kernel (largest summed HIP-event time) against the 8 TB/s HBM peak:
                 algorithmic HBM bytes per launch / average launch duration (see roofline()); every
                 stage's figures under `stages` (HBM GB/s, and for an LDS-staged BVH the algorithmic
@@ -98,10 +104,23 @@ def parse():
                         "multi-process flow with several ranks on one GPU")
     p.add_argument("--dump-framebuffer", default=None,
                    help="rank 0 saves the reduced RGBW framebuffer of the timed steps (.npy) before the roofline pass")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps rank 0 writes what they computed, the (reduced) RGBW framebuffer a "
+                        "caller of nh_render reads back, as DIR/framebuffer.npy (float32; above 64 MB a fixed seeded "
+                        "sample of its elements)")
+    p.add_argument("--full", action="store_true",
+                   help="also everything beside the headline figure: the calibration launch and the roofline / "
+                        "traversal records, the serialized roofline pass, cpu_baseline, denoise, traversal_1m, "
+                        "strong_c4, megakernel, denoiser_test and project_scenes (each still has its own switch); "
+                        "without it the run sets up, warms up, times --steps steps and prints the line")
     p.add_argument("--launcher-selftest", action="store_true",
                    help="only rendezvous: every rank all-reduces its rank over gloo and rank 0 prints the world size "
                         "(tests the --gpus N launcher without a GPU)")
     a = p.parse_args()
+    if not a.full:
+        # a plain run measures the headline figure only: every other record's own switch is set to "skip"
+        a.no_calibrate = a.no_cpu = a.no_denoise = a.no_extras = True
+        a.roofline_steps = a.strong_spp = a.traversal_1m_steps = 0
     a.config_given = a.config is not None
     a.config = a.config or "c2"
     return a
@@ -516,6 +535,8 @@ def run_workload(nh, args, config, steps, warmup, local, blocks=None, world=1, r
         elapsed = max_over_ranks(elapsed, dist, args, local)
     if args.dump_framebuffer and rank == 0:
         np.save(args.dump_framebuffer, reduced if reduced is not None else ctx.framebuffer())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"framebuffer": reduced if reduced is not None else ctx.framebuffer()})
     st = ctx.stats()
     pools = int(st.get("pools_active", 0)) if a.mode == "wavefront" else 0  # path pools of the timed steps
     # chunks of the timed steps and how many of their tails ran decoupled from their path pool (tail slots)
@@ -546,6 +567,22 @@ def run_workload(nh, args, config, steps, warmup, local, blocks=None, world=1, r
     return {"scene": scene, "W": W, "H": H, "R": R, "desc": scene_desc, "elapsed": elapsed, "samples": samples,
             "roof": roof, "bvh_s": bvh_s, "upload_s": upload_s, "ctx": ctx, "chunks": chunks,
             "pools": pools, "ranks": ranks}
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: DIR/<name>.npy (float32) per output array of the timed steps; at most 64 MB in all, larger
+    arrays as a fixed seeded sample of their elements (the same elements in every run of the same shape)."""
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_MAX_BYTES // max(len(arrays), 1) // 4  # elements per array
+    for name, arr in arrays.items():
+        arr = np.ascontiguousarray(arr, dtype=np.float32)
+        if arr.size > budget:
+            idx = np.sort(np.random.default_rng(0).integers(0, arr.size, size=budget // 2))
+            arr = arr.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def reduce_framebuffer(ctx, dist, args, local, rank):
@@ -636,7 +673,7 @@ def traversal_1m(nh, args, local):
     """perf-1M: the north star's traversal roofline target is set on the BVH-traversal
     kernel of the ~1M-triangle scene at 1 GPU; measured here in the same run (a short bench of it)."""
     a = argparse.Namespace(**vars(args))
-    a.dump_framebuffer = None
+    a.dump_framebuffer = a.dump_outputs = None
     r = run_workload(nh, a, "bumpy1m", args.traversal_1m_steps, 1, local)
     roof = r["roof"]
     stage = "trace" if "trace" in roof["stages"] else "extend"
@@ -718,7 +755,7 @@ def megakernel_record(nh, args, local):
     """BASELINE configs[1] names "megakernel vs wavefront": the same C2 workload through nh_path_kernel (one thread
     per (pixel, round) runs the whole path_mis loop), --rounds rounds per step."""
     a = argparse.Namespace(**vars(args))
-    a.mode, a.dump_framebuffer, a.no_calibrate, a.pools = "megakernel", None, True, 0
+    a.mode, a.dump_framebuffer, a.dump_outputs, a.no_calibrate, a.pools = "megakernel", None, None, True, 0
     r = run_workload(nh, a, "c2", 2, 1, local)
     st = r["ctx"].stats()
     r["ctx"].close()

@@ -22,16 +22,19 @@ python3 scripts/pmc_traffic.py gpurun_out/pmc_${tag}_bumpy1m bumpy1m_1024x1024_r
 python3 scripts/pmc_traffic.py gpurun_out/pmc_${tag}_c5 c5_4096x4096_r16_ordered_wavefront/extend "wf_trace_pt<64, true, false, false, true>" || exit 97
 python3 scripts/pmc_traffic.py gpurun_out/pmc_${tag}_c5 c5_4096x4096_r16_ordered_wavefront/shadow "wf_trace_pt<64, true, true, false, true>" || exit 97
 cp profiles/pmc_traffic.json gpurun_out/pmc_traffic_$tag.json
-scripts/gpu_step.sh 500 gpurun_out/bench_$tag.log python bench.py || exit 99
+# the bench lines and the trace go to $NH_OUT (default bench_out/); --full: every record of the line, not the headline alone
+out=${NH_OUT:-bench_out}
+mkdir -p $out
+scripts/gpu_step.sh 500 $out/bench_$tag.log python bench.py --full || exit 99
 for cfg in c1 c3 c4 c5 bumpy1m; do
-  scripts/gpu_step.sh 400 gpurun_out/bench_${tag}_$cfg.log python bench.py --config $cfg --no-cpu --no-denoise --no-extras --strong-spp 0 --traversal-1m-steps 0 || exit 99
+  scripts/gpu_step.sh 400 $out/bench_${tag}_$cfg.log python bench.py --full --config $cfg --no-cpu --no-denoise --no-extras --strong-spp 0 --traversal-1m-steps 0 || exit 99
 done
-grep -h "^{" gpurun_out/bench_$tag.log gpurun_out/bench_${tag}_*.log > gpurun_out/bench_lines_$tag.jsonl
+grep -h "^{" $out/bench_$tag.log $out/bench_${tag}_*.log > $out/bench_lines_$tag.jsonl
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/trace_$tag -o run -- python3 bench.py --no-cpu > gpurun_out/trace_$tag.log 2>&1 || { echo "trace failed"; tail -5 gpurun_out/trace_$tag.log; exit 99; }
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_$tag -o run -- python3 bench.py --full --no-cpu > $out/trace_$tag.log 2>&1 || { echo "trace failed"; tail -5 $out/trace_$tag.log; exit 99; }
 cat gpurun_out/smoke_$tag.log
 python3 -c "
 import json
-for l in open('gpurun_out/bench_lines_$tag.jsonl'):
+for l in open('$out/bench_lines_$tag.jsonl'):
     d = json.loads(l); r = d.get('roofline') or {}
     print(d['config']['config'], d['value'], 'frac', r.get('frac'), 'traffic', r.get('traffic'), 'limiter', bool(r.get('limiter')))"

@@ -26,6 +26,8 @@ Writes (all data, no reference source):
                           the `normals` integrator's normals-identity{,-x,-y,-ref}.xml, normals-primitives.xml) with
                           their meshes and the shipped normal maps res/normal-identity{,-x,-y}.png,
                           normal-primitives.png, normal-test.png (same form)
+  envmap-test.png         the shipped scenes/project/res/envmap-test.png as it is (no scene bundle holds it; the texel
+                          pin of tests/test_normalmap.py reads it)
 """
 import base64
 import gzip
@@ -184,8 +186,11 @@ def main():
     normalmap = {p: read_fixture(ref, p) for p in NORMALMAP_FILES}
     with open(os.path.join(HERE, "normalmap_scenes.json.gz"), "wb") as f:
         f.write(gzip.compress(json.dumps(normalmap, indent=0).encode(), mtime=0))
+    with open(os.path.join(ref, "scenes/project/res/envmap-test.png"), "rb") as src, \
+            open(os.path.join(HERE, "envmap-test.png"), "wb") as f:
+        f.write(src.read())
     print("wrote pcg32_kat.json, reference_scenes.json, textured_scenes.json.gz, project_scenes.json.gz, "
-          "normalmap_scenes.json.gz")
+          "normalmap_scenes.json.gz, envmap-test.png")
 
 
 if __name__ == "__main__":

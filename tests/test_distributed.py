@@ -130,10 +130,10 @@ def test_bench_hip_ranks_strong_scaling_equals_one_rank_render(tmp_path, gpu, wo
     import nori_hip as nh
     import scenegen
     out = str(tmp_path / "reduced.npy")
-    line = _bench(["--gpus", str(world), "--dist-backend", "gloo", "--scaling", "strong", "--config", "c1", "--width",
-                   "160", "--height", "96", "--rounds", "3", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-denoise",
-                   "--traversal-1m-steps", "0", "--roofline-steps", "0", "--strong-spp", "2", "--no-extras",
-                   "--dump-framebuffer", out])
+    line = _bench(["--full", "--gpus", str(world), "--dist-backend", "gloo", "--scaling", "strong", "--config", "c1",
+                   "--width", "160", "--height", "96", "--rounds", "3", "--steps", "2", "--warmup", "1", "--no-cpu",
+                   "--no-denoise", "--traversal-1m-steps", "0", "--roofline-steps", "0", "--strong-spp", "2",
+                   "--no-extras", "--dump-framebuffer", out])
     assert line["n_gpus"] == world and line["scaling"] == "strong" and line["config"]["spp"] == 6
     sc = line["strong_c4"]
     assert sc["n_gpus"] == world and sc["spp"] == 2 and sc["msamples_s"] > 0
