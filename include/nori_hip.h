@@ -284,6 +284,11 @@ typedef struct nh_render_req {
     int32_t collect_stats;        /* 1: count BVH nodes/prims visited (calibration, slower) */
 } nh_render_req;
 
+/* LDS budget (bytes) of the scene tables the diffuse area-light bounce kernels stage beside a small BVH: 64 per shape,
+   48 per BSDF, 32 per emitter, the emitting meshes' area CDFs (4 per entry, rounded up to 16) and 48 per emitting
+   face. A scene over it renders with the general kernels (nh_render_stats::bounce_traits = 1). */
+#define NH_SMALL_TABLES_BYTES 4096
+
 typedef struct nh_render_stats {
     double kernel_ms_path;        /* summed device time of the path-tracing kernel(s) */
     double kernel_ms_splat;       /* summed device time of the ImageBlock splat kernel */
@@ -347,6 +352,10 @@ typedef struct nh_render_stats {
        the survivors (clock64, summed over lanes), and the path-bounces it ran */
     uint64_t bounce_cycles_load, bounce_cycles_body, bounce_cycles_shadow, bounce_cycles_closest, bounce_cycles_head;
     uint64_t bounce_cycles_store, bounce_bounces;
+    /* which instantiation of the RR-ahead bounce kernel the last wavefront render ran: 0 none (another pipeline),
+       1 the general kernels, 2 the diffuse area-light ones (path_mis, every BSDF diffuse with a constant albedo, every
+       light an area light on a mesh, no envmap, normal map or thin lens; NH_BOUNCE_TRAITS=0 forces 1) */
+    uint64_t bounce_traits;
 } nh_render_stats;
 
 typedef struct nh_scene nh_scene;

@@ -83,6 +83,7 @@ struct WfPool {
     bool persistent = false, wide = false, trace2 = false, tail = false, draining = false;
     bool fused = false, sorted = false;  // one wf_bounce kernel per bounce (LDS-staged BVH); material-sorted queue
     bool rr = false;                     // fused kernels with the next vertex's Russian roulette ahead (wf_bounce_rr)
+    bool trait = false;                  // RR-ahead kernels' diffuse area-light instantiations (nh_ctx::diffuse_area)
     bool shade_sorted = false;           // wf_shade entries in BSDF-type order (deep BVHs, mixed materials)
     int64_t tail_at = 0, drain_at = 0;
     int it = 0;
@@ -143,6 +144,19 @@ struct nh_ctx {
     bool specular = false;             // a mirror or dielectric BSDF: long discrete chains, long chunk tails
     bool textured = false;             // a BSDF with an albedo texture
     bool normal_mapped = false;        // a shape with a normal map (the full bounce / tail bodies' NMAP instantiation)
+    // path_mis, every BSDF diffuse with a constant albedo, every light an area light on a mesh with an emit_faces
+    // record, no envmap, normal map or thin lens: the RR-ahead kernels' trait instantiations apply
+    bool diffuse_area = false;
+    // host copies of the scene tables and the emit_faces count, for the LDS image of a small scene (build_small_image)
+    std::vector<nhd::DShape> h_shapes;
+    std::vector<nhd::DBsdf> h_bsdfs;
+    std::vector<nhd::DEmitter> h_emitters;
+    std::vector<float> h_area_cdf;
+    int n_emit_faces = 0;
+    // the LDS image of a small scene (WfLaunch::small_image; owned by bvh_bufs) and its table regions' float4 counts
+    // (all 0: tables not staged)
+    float4 *small_image = nullptr;
+    int small_tab[5] = {0, 0, 0, 0, 0};
     float *fb = nullptr;
     size_t fb_floats = 0;
     float *rec = nullptr;  // (r, g, b) per sample
@@ -695,6 +709,23 @@ int nh_upload_scene(nh_ctx *c, const nh_scene_desc *d) {
     c->normal_mapped = false;
     for (uint32_t i = 0; i < d->n_shapes; ++i) c->normal_mapped = c->normal_mapped || d->shapes[i].normal_map != 0;
     c->textured = c->textured || c->normal_mapped;
+    c->diffuse_area = S.integrator == NH_INTEGRATOR_PATH_MIS && !c->textured && !S.dof && d->envmap < 0 &&
+                      d->n_emitters > 0;
+    for (uint32_t i = 0; i < d->n_bsdfs; ++i) c->diffuse_area = c->diffuse_area && d->bsdfs[i].type == NH_BSDF_DIFFUSE;
+    for (uint32_t i = 0; i < d->n_emitters; ++i) {
+        const nh_emitter &e = d->emitters[i];
+        c->diffuse_area = c->diffuse_area && e.type == NH_EMITTER_AREA && e.shape >= 0 &&
+                          (uint32_t)e.shape < d->n_shapes && ds[e.shape].ef_off >= 0;
+    }
+    // (a shape's emitter index must be one of those: shade_head reads S.emitters[shape.emitter])
+    for (uint32_t i = 0; i < d->n_shapes; ++i)
+        c->diffuse_area = c->diffuse_area && d->shapes[i].emitter < (int32_t)d->n_emitters;
+    c->h_shapes = ds;
+    c->h_bsdfs = db;
+    c->h_emitters = de;
+    c->h_area_cdf.assign(d->area_cdf, d->area_cdf + d->n_area_cdf);
+    c->n_emit_faces = (int)ef_tri.size();
+    c->small_image = nullptr;  // (the BVH and its image went with bvh_bufs above)
     c->V.assign(d->V, d->V + 3 * nv);
     c->F.assign(d->F, d->F + 3 * (size_t)d->n_faces);
     c->width = d->camera.width;
@@ -975,6 +1006,83 @@ static int number_top_first(std::vector<float4> &wide, const float root_min[3], 
     return (int)order.size();
 }
 
+// The LDS image of a small scene (WfLaunch::small_image), rebuilt by every BVH upload (a scene upload drops the BVH):
+// nodes, primitive records and leaf table copied from the uploaded arrays, the pair records and flat-triangle frames
+// computed on the device by the float operations the kernels' staging ran per workgroup before (launch_small_image),
+// and -- for a scene the diffuse area-light kernels run on, within kSmallTablesBytes -- the scene tables: shapes,
+// BSDFs, emitters, the emitting meshes' area CDFs packed one after the other (the image's shape records index them)
+// and the emit_faces records. Frames are part of the image whenever the scene is small enough for them; a render
+// that does not want them copies the image without its last region.
+static int build_small_image(nh_ctx *c) {
+    c->small_image = nullptr;
+    for (int &v : c->small_tab) v = 0;
+    const size_t scene_bytes = 16 * (size_t)(c->n_node_f4 + c->n_prim_f4) + 8 * (size_t)c->n_leaves;
+    if (scene_bytes > kSmallSceneBytes) return NH_OK;
+    const int n = c->n_prim_f4 / 3;
+    const int leaves_f4 = (c->n_leaves + 1) / 2;
+    const int pairs_off = c->n_node_f4 + c->n_prim_f4 + leaves_f4;
+    const bool frames = n <= kSmallFramesMaxPrims;
+    std::vector<float4> tab;
+    if (c->diffuse_area) {
+        std::vector<nhd::DShape> sh = c->h_shapes;
+        std::vector<float> cdf;
+        for (const nhd::DEmitter &e : c->h_emitters) {  // (diffuse_area: every emitter's shape is a mesh)
+            nhd::DShape &s = sh[e.shape];
+            if ((size_t)s.pdf_off + s.n_faces + 1 > c->h_area_cdf.size()) return fail(c, "area CDF out of range"), NH_ERR_INVALID;
+            const int off = (int)cdf.size();
+            cdf.insert(cdf.end(), c->h_area_cdf.begin() + s.pdf_off, c->h_area_cdf.begin() + s.pdf_off + s.n_faces + 1);
+            s.pdf_off = off;
+        }
+        cdf.resize((cdf.size() + 3) / 4 * 4, 0.f);
+        const size_t bytes = sh.size() * sizeof(nhd::DShape) + c->h_bsdfs.size() * sizeof(nhd::DBsdf) +
+                             c->h_emitters.size() * sizeof(nhd::DEmitter) + cdf.size() * sizeof(float) +
+                             3 * (size_t)c->n_emit_faces * sizeof(float4);
+        if (bytes <= kSmallTablesBytes) {
+            static_assert(sizeof(nhd::DShape) % 16 == 0 && sizeof(nhd::DBsdf) % 16 == 0 && sizeof(nhd::DEmitter) % 16 == 0,
+                          "table records are whole float4s");
+            c->small_tab[0] = (int)(sh.size() * sizeof(nhd::DShape) / 16);
+            c->small_tab[1] = (int)(c->h_bsdfs.size() * sizeof(nhd::DBsdf) / 16);
+            c->small_tab[2] = (int)(c->h_emitters.size() * sizeof(nhd::DEmitter) / 16);
+            c->small_tab[3] = (int)(cdf.size() / 4);
+            c->small_tab[4] = 3 * c->n_emit_faces;
+            tab.resize((size_t)c->small_tab[0] + c->small_tab[1] + c->small_tab[2] + c->small_tab[3]);
+            char *w = reinterpret_cast<char *>(tab.data());
+            std::memcpy(w, sh.data(), sh.size() * sizeof(nhd::DShape));
+            w += sh.size() * sizeof(nhd::DShape);
+            std::memcpy(w, c->h_bsdfs.data(), c->h_bsdfs.size() * sizeof(nhd::DBsdf));
+            w += c->h_bsdfs.size() * sizeof(nhd::DBsdf);
+            std::memcpy(w, c->h_emitters.data(), c->h_emitters.size() * sizeof(nhd::DEmitter));
+            w += c->h_emitters.size() * sizeof(nhd::DEmitter);
+            std::memcpy(w, cdf.data(), cdf.size() * sizeof(float));
+        }
+    }
+    const int tab_f4 = (int)tab.size() + c->small_tab[4];
+    const int frames_off = pairs_off + nhd::kPairF4 * n + tab_f4;
+    const size_t total = (size_t)frames_off + (frames ? 3 * (size_t)n : 0);
+    float4 *img = nullptr;
+    HIP_TRY(c, hipMalloc(&img, std::max<size_t>(total, 1) * sizeof(float4)));
+    c->bvh_bufs.push_back(img);
+    HIP_TRY(c, hipMemsetAsync(img, 0, std::max<size_t>(total, 1) * sizeof(float4), c->stream));
+    const auto d2d = [&](float4 *dst, const void *src, size_t bytes) {
+        return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->stream) : hipSuccess;
+    };
+    HIP_TRY(c, d2d(img, c->tv.nodes, 16 * (size_t)c->n_node_f4));
+    HIP_TRY(c, d2d(img + c->n_node_f4, c->tv.prims, 16 * (size_t)c->n_prim_f4));
+    HIP_TRY(c, d2d(img + c->n_node_f4 + c->n_prim_f4, c->tv.leaves, 8 * (size_t)c->n_leaves));
+    if (n > 0) {
+        nh::launch_small_image(c->tv, c->n_prim_f4, pairs_off, frames ? frames_off : -1, img, c->stream);
+        HIP_TRY(c, hipGetLastError());
+    }
+    if (!tab.empty()) {
+        float4 *t = img + pairs_off + nhd::kPairF4 * n;
+        HIP_TRY(c, hipMemcpyAsync(t, tab.data(), tab.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, d2d(t + tab.size(), c->S.emit_faces, 16 * (size_t)c->small_tab[4]));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));  // (tab is a local)
+    }
+    c->small_image = img;
+    return NH_OK;
+}
+
 int nh_upload_bvh(nh_ctx *c, const nh_bvh_desc *b) {
     if (!c || !b) return NH_ERR_INVALID;
     if (!c->has_scene) return fail(c, "nh_upload_bvh: upload the scene first"), NH_ERR_STATE;
@@ -1120,6 +1228,7 @@ int nh_upload_bvh(nh_ctx *c, const nh_bvh_desc *b) {
     c->depth = (int)tree_depth + 2;
     if (!c->d_scene) HIP_TRY(c, hipMalloc(&c->d_scene, sizeof(nhd::DScene)));
     HIP_TRY(c, hipMemcpyAsync(c->d_scene, &c->S, sizeof(nhd::DScene), hipMemcpyHostToDevice, c->stream));
+    if ((rc = build_small_image(c))) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->has_bvh = true;
     return NH_OK;
@@ -1391,6 +1500,8 @@ static int pool_start(nh_ctx *c, WfPool &p, const WfJob &job) {
         // normalize + frame construction per hit) while they add little LDS
         L.small_frames = c->n_prim_f4 / 3 <= kSmallFramesMaxPrims;
         if (const char *e = std::getenv("NH_LDS_FRAMES")) L.small_frames = L.small_frames && e[0] != '0';
+        L.small_image = c->small_image;
+        for (int i = 0; i < 5; ++i) L.small_tab[i] = c->small_tab[i];
     }
     const int per_chunk = 256;  // wf_shade's chunk
     const int max_chunks = (n_paths + per_chunk - 1) / per_chunk;
@@ -1434,6 +1545,12 @@ static int pool_start(nh_ctx *c, WfPool &p, const WfJob &job) {
     p.shade_sorted = false;
     if (const char *e = std::getenv("NH_SORT_SHADE")) p.shade_sorted = !p.fused && e[0] == '1';
     if (const char *e = std::getenv("NH_SORT")) p.sorted = p.fused && e[0] == '1';
+    // the diffuse area-light instantiations of the RR-ahead kernels (near-first traversal, one material class);
+    // NH_BOUNCE_TRAITS=0: the general lean kernels (A/B, tests)
+    // (their scene tables come from the LDS image: a scene over the table budget takes the general kernels)
+    p.trait = p.rr && c->diffuse_area && c->small_tab[0] > 0 && j.ordered && !p.sorted;
+    if (const char *e = std::getenv("NH_BOUNCE_TRAITS")) p.trait = p.trait && e[0] != '0';
+    c->stats.bounce_traits = p.rr ? (p.trait ? 2 : 1) : 0;
     c->stats.fused_bounce = p.fused ? 1 : 0;
     c->stats.node_bytes = p.wide ? 16 * nhd::kWideF4 * (c->wide_w / 4) : 64;
     c->stats.lds_scene = small && !p.persistent && c->depth <= 16 ? 1 : 0;  // the SMALL instantiations (DEPTH 16)
@@ -1487,6 +1604,7 @@ static void chunk_swap(WfPool &a, WfPool &b) {
     std::swap(a.fused, b.fused);
     std::swap(a.sorted, b.sorted);
     std::swap(a.rr, b.rr);
+    std::swap(a.trait, b.trait);
     std::swap(a.shade_sorted, b.shade_sorted);
     std::swap(a.tail_at, b.tail_at);
     std::swap(a.drain_at, b.drain_at);
@@ -1532,7 +1650,7 @@ static int pool_handoff(nh_ctx *c, WfPool &p, WfPool &T, int bound, hipEvent_t *
     HIP_TRY(c, hipEventRecord(ev[1], T.stream));
     HIP_TRY(c, hipEventRecord(ev[2], T.stream));
     nh::launch_wf_tail_rr(c->d_scene, c->tv, L, T.job.ordered, T.job.stats, bound, c->specular,
-                          !c->specular && !c->textured, c->normal_mapped, T.stream);
+                          !c->specular && !c->textured, c->normal_mapped, T.trait, T.stream);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(ev[3], T.stream));
     T.tail = true;
@@ -1598,7 +1716,7 @@ static int pool_enqueue(nh_ctx *c, WfPool &p) {
         if (it > 0 && (int64_t)bound <= p.tail_at) {
             if (p.rr)
                 nh::launch_wf_tail_rr(c->d_scene, c->tv, L, ordered, stats, bound, c->specular, !c->specular && !c->textured,
-                                      c->normal_mapped, p.stream);
+                                      c->normal_mapped, p.trait, p.stream);
             else nh::launch_wf_tail(c->d_scene, c->tv, L, ordered, stats, false, bound, c->depth, p.stream);
             HIP_TRY(c, hipGetLastError());
             HIP_TRY(c, hipEventRecord(ev[3], p.stream));
@@ -1608,7 +1726,7 @@ static int pool_enqueue(nh_ctx *c, WfPool &p) {
             return NH_OK;
         }
         if (p.rr) nh::launch_wf_bounce_rr(c->d_scene, c->tv, L, ordered, stats, p.sorted, !c->specular && !c->textured,
-                                          c->normal_mapped, bound, p.stream);
+                                          c->normal_mapped, p.trait, bound, p.stream);
         else nh::launch_wf_bounce(c->d_scene, c->tv, L, ordered, stats, p.sorted, bound, p.stream);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipEventRecord(ev[3], p.stream));

@@ -5,6 +5,7 @@
 
 #include "nh_device.h"
 #include "nh_traverse.h"
+#include "nori_hip.h"
 
 struct RayBatch {
     const float *ox, *oy, *oz, *dx, *dy, *dz, *mint, *maxt;
@@ -177,6 +178,13 @@ struct WfLaunch {
     // kernels (0 = traverse from HBM)
     int small_nodes, small_leaves, small_prims;
     int small_frames;  // 1: the fused kernels also stage the flat triangles' shading frames (Traversal::frames)
+    // The LDS image of a small scene, built once per upload (nh_api.hip build_small_image): float4 regions in this
+    // order -- nodes, primitive records, leaf table, pair records, scene tables, flat-triangle frames -- which the
+    // fused kernels copy as it stands (stage_small_scene). small_tab: float4 counts of the table regions (shapes,
+    // bsdfs, emitters, the emitting meshes' area CDFs, emit_faces), all 0 when the tables are not staged (over
+    // kSmallTablesBytes, or a scene the diffuse area-light kernels do not run on): only those kernels read them.
+    const float4 *small_image;
+    int small_tab[5];
     // persistent traversal: per-lane stack spill area (kPersistentBlocks * 128 lanes x spill_depth
     // 32-bit words; the 4-wide traversal spills (ref, distance) pairs)
     uint32_t *trav_spill;
@@ -187,6 +195,10 @@ struct WfLaunch {
 constexpr int kPersistentBlocks = 256 * 16;
 constexpr size_t kSmallSceneBytes = 16384;
 constexpr int kSmallFramesMaxPrims = 256;  // frames staged (48 B per record) only for scenes this small
+// LDS budget of the scene tables staged beside a small BVH (shapes 64 B, BSDFs 48 B, emitters 32 B each, the emitting
+// meshes' area CDFs, 48 B per emitting face): the Cornell box needs under 1 KB; 4 KB keeps four bounce workgroups
+// per CU (each 16 KB of stacks + the scene copy) inside the CU's 160 KB
+constexpr size_t kSmallTablesBytes = NH_SMALL_TABLES_BYTES;
 namespace nh {
 void launch_wf_trace(const nhd::DScene *S, const nhd::Traversal &tv, const WfLaunch &L, bool ordered, bool stats,
                      bool shadow, bool persistent, int wide, int bound, int depth, hipStream_t st);
@@ -206,14 +218,26 @@ void launch_wf_bounce(const nhd::DScene *S, const nhd::Traversal &tv, const WfLa
 // vertex's Russian roulette
 // lean: the FULL = false body (no mirror / dielectric BSDF, no texture); nmap: the scene has shape normal maps (else the
 // full body is the NMAP = false instantiation)
+// trait: the scene qualifies for the diffuse area-light instantiations (launch_wf_bounce_trait / launch_wf_tail_trait),
+// taken when the other arguments allow them (near-first traversal, unsorted queue, the lean 2-wave tail)
 void launch_wf_bounce_rr(const nhd::DScene *S, const nhd::Traversal &tv, const WfLaunch &L, bool ordered, bool stats, bool sort,
-                         bool lean, bool nmap, int bound, hipStream_t st);
+                         bool lean, bool nmap, bool trait, int bound, hipStream_t st);
 void launch_wf_tail_rr(const nhd::DScene *S, const nhd::Traversal &tv, const WfLaunch &L, bool ordered, bool stats, int bound,
-                       bool specular, bool lean, bool nmap, hipStream_t st);
+                       bool specular, bool lean, bool nmap, bool trait, hipStream_t st);
+// wf_bounce_rr / wf_tail_rr<.., TRAIT = true>: near-first traversal, unsorted queue; bounce 0 (L.first) and the later
+// bounces are separate instantiations. Their own translation-unit part of nh_wavefront.hip.
+void launch_wf_bounce_trait(const nhd::DScene *S, const nhd::Traversal &tv, const WfLaunch &L, bool stats, int bound,
+                            hipStream_t st);
+void launch_wf_tail_trait(const nhd::DScene *S, const nhd::Traversal &tv, const WfLaunch &L, bool stats, int bound,
+                          int coop, hipStream_t st);
 void launch_wf_tail(const nhd::DScene *S, const nhd::Traversal &tv, const WfLaunch &L, bool ordered, bool stats,
                     int wide, int bound, int depth, hipStream_t st);
 // copies the live RR-ahead paths of L's input queue (at most bound) densely into dst, count into dst_counts[0]
 void launch_wf_pack_rr(const WfLaunch &L, const WfBuf &dst, unsigned *dst_counts, int bound, hipStream_t st);
 // n_copy count words src -> host_dst (pinned, device-visible), then n_zero words of zero cleared (wf_counts_kernel)
+// the computed regions of a small scene's LDS image (pair records at float4 pairs_off, frames at frames_off or none
+// if < 0), from n_prim_f4 / 3 primitive records, by the float operations the kernels' own staging used to run
+void launch_small_image(const nhd::Traversal &tv, int n_prim_f4, int pairs_off, int frames_off, float4 *image,
+                        hipStream_t st);
 void launch_wf_counts(const unsigned *src, unsigned *host_dst, int n_copy, unsigned *zero, int n_zero, hipStream_t st);
 }  // namespace nh

@@ -31,12 +31,14 @@ __device__ __noinline__ F3 tex_eval(const DTex *texs, const float4 *texels, int 
 #else
 #define NH_NMAP_ON true
 #endif
+// shapes: the shape table (S.shapes, or a copy of it)
 template <bool NMAP_ = true>
-__device__ __forceinline__ void hit_info(const DScene &S, const Traversal &tv, const Hit &h, F3 o, F3 d, Its &its) {
+__device__ __forceinline__ void hit_info(const DScene &S, const DShape *shapes, const Traversal &tv, const Hit &h, F3 o,
+                                         F3 d, Its &its) {
     constexpr bool NMAP = NMAP_ && NH_NMAP_ON;
     const float4 a = tv.prims[3 * h.k], b = tv.prims[3 * h.k + 1];
     const int shape = __float_as_int(b.w);
-    const DShape sh = S.shapes[shape];
+    const DShape sh = shapes[shape];
     its.shape = shape;
     if (sh.type == SHAPE_SPHERE) {
         its.p = add(o, scl(h.t, d));
@@ -101,6 +103,10 @@ __device__ __forceinline__ void hit_info(const DScene &S, const Traversal &tv, c
     } else {
         its.sh = tv.frames ? staged_frame(tv.frames, h.k) : frame_from_n(normalized(cross(sub(p1, p0), sub(p2, p0))));
     }
+}
+template <bool NMAP_ = true>
+__device__ __forceinline__ void hit_info(const DScene &S, const Traversal &tv, const Hit &h, F3 o, F3 d, Its &its) {
+    hit_info<NMAP_>(S, S.shapes, tv, h, o, d, its);
 }
 
 
@@ -210,19 +216,32 @@ __device__ __forceinline__ float env_pdf(const DScene &S, F3 wi) {  // EnvMap::p
 }
 
 // AreaEmitter / PointLight / EnvMap (src/emitters/arealight.cpp:58-125, pointlight.cpp:47-78)
-__device__ __forceinline__ float emitter_pdf(const DScene &S, const DEmitter &e, F3 ref, F3 p, F3 n, F3 wi) {
+// AREA_MESH (the diffuse area-light instantiations of the RR-ahead kernels, nh_wavefront.hip): the caller knows e is an
+// area light on a mesh with an emit_faces record, so only that path is compiled -- the same operations on it.
+// shapes: the table e.shape indexes (S.shapes, or a copy of it)
+template <bool AREA_MESH = false>
+__device__ __forceinline__ float emitter_pdf(const DScene &S, const DShape *shapes, const DEmitter &e, F3 ref, F3 p,
+                                             F3 n, F3 wi) {
+    if constexpr (AREA_MESH) {
+        if (dot(n, neg(wi)) < 0.f) return 0.f;
+        return shapes[e.shape].pdf_norm * dot(sub(p, ref), sub(p, ref)) / fabsf(dot(n, neg(wi)));
+    }
     if (e.type == EMITTER_ENVMAP) return env_pdf(S, wi);
     if (e.type == EMITTER_POINT) return 1.f;
     if (dot(n, neg(wi)) < 0.f) return 0.f;
-    const DShape sh = S.shapes[e.shape];
+    const DShape sh = shapes[e.shape];
     // Sphere::pdfSurface: std::pow(1.f / r, 2) (double, exact square) * (0.25f / M_PI)
     float prob = sh.type == SHAPE_MESH
                      ? sh.pdf_norm
                      : (float)((double)(1.f / sh.radius) * (double)(1.f / sh.radius) * (double)(0.25f / kPi));
     return prob * dot(sub(p, ref), sub(p, ref)) / fabsf(dot(n, neg(wi)));
 }
+__device__ __forceinline__ float emitter_pdf(const DScene &S, const DEmitter &e, F3 ref, F3 p, F3 n, F3 wi) {
+    return emitter_pdf<false>(S, S.shapes, e, ref, p, n, wi);
+}
+template <bool AREA_MESH = false>
 __device__ __forceinline__ F3 emitter_eval(const DEmitter &e, F3 ref, F3 n, F3 wi) {
-    if (e.type == EMITTER_POINT) {
+    if (!AREA_MESH && e.type == EMITTER_POINT) {
         F3 dd = sub(ref, f3(e.px, e.py, e.pz));
         float q = dot(dd, dd);
         return f3(e.lr / q, e.lg / q, e.lb / q);
@@ -237,9 +256,11 @@ struct ESample {
     float smint, smaxt;
 };
 
-__device__ __forceinline__ F3 emitter_sample(const DScene &S, const DEmitter &e, F3 ref, float sx, float sy,
-                                             ESample &es) {
-    if (e.type == EMITTER_ENVMAP) {  // EnvMap::sample (environmentmap.cpp:73-101)
+// ST: where the scene tables are read from (S itself, or a view of copies: nh_wavefront.hip SceneTables)
+template <bool AREA_MESH = false, class ST = DScene>
+__device__ __forceinline__ F3 emitter_sample(const DScene &S, const ST &T, const DEmitter &e, F3 ref, float sx,
+                                             float sy, ESample &es) {
+    if (!AREA_MESH && e.type == EMITTER_ENVMAP) {  // EnvMap::sample (environmentmap.cpp:73-101)
         const unsigned W = (unsigned)S.env_w, H = (unsigned)S.env_h;
         const unsigned elem = (unsigned)(S.env_guide ? dpdf_sample_guided(S.env_cdf, (int)(W * H), sx, S.env_guide,
                                                                           S.env_guide_bits)
@@ -259,7 +280,7 @@ __device__ __forceinline__ F3 emitter_sample(const DScene &S, const DEmitter &e,
         const F3 ev = env_eval(S, es.wi);
         return f3(ev.x / pdf, ev.y / pdf, ev.z / pdf);
     }
-    if (e.type == EMITTER_POINT) {
+    if (!AREA_MESH && e.type == EMITTER_POINT) {
         F3 pos = f3(e.px, e.py, e.pz);
         F3 rp = sub(ref, pos);
         es.so = pos;
@@ -271,16 +292,16 @@ __device__ __forceinline__ F3 emitter_sample(const DScene &S, const DEmitter &e,
         es.n = f3(0, 0, 0);
         return emitter_eval(e, ref, es.n, es.wi);
     }
-    const DShape sh = S.shapes[e.shape];
+    const DShape sh = T.shapes[e.shape];
     F3 p, n;
-    if (sh.type == SHAPE_MESH) {  // Mesh::sampleSurface (mesh.cpp:50-71)
-        const float *cdf = S.area_cdf + sh.pdf_off;
+    if (AREA_MESH || sh.type == SHAPE_MESH) {  // Mesh::sampleSurface (mesh.cpp:50-71)
+        const float *cdf = T.area_cdf + sh.pdf_off;
         int idt = dpdf_sample(cdf, sh.n_faces, sx);
         sx = (sx - cdf[idt]) / (cdf[idt + 1] - cdf[idt]);
         float su1 = f_sqrt(sx);  // squareToUniformTriangle (warp.cpp:162-166)
         float bu = 1.f - su1, bv = sy * su1, bw = 1.f - bu - bv;
-        if (sh.ef_off >= 0) {  // the face's vertices and its normal, precomputed (DScene::emit_faces)
-            const float4 *q = S.emit_faces + 3 * (size_t)(sh.ef_off + idt);
+        if (AREA_MESH || sh.ef_off >= 0) {  // the face's vertices and its normal, precomputed (DScene::emit_faces)
+            const float4 *q = T.emit_faces + 3 * (size_t)(sh.ef_off + idt);
             const float4 q0 = q[0], q1 = q[1], q2 = q[2];
             p = add(add(scl(bu, f3(q0.x, q0.y, q0.z)), scl(bv, f3(q1.x, q1.y, q1.z))), scl(bw, f3(q2.x, q2.y, q2.z)));
             n = f3(q0.w, q1.w, q2.w);
@@ -307,10 +328,14 @@ __device__ __forceinline__ F3 emitter_sample(const DScene &S, const DEmitter &e,
     es.sd = neg(es.wi);
     es.smint = kEps;
     es.smaxt = f_sqrt(dot(pr, pr)) - kEps;
-    float probs = emitter_pdf(S, e, ref, p, n, es.wi);
+    float probs = emitter_pdf<AREA_MESH>(S, T.shapes, e, ref, p, n, es.wi);
     if (fabsf(probs) < kEps) return f3(0, 0, 0);
-    F3 ev = emitter_eval(e, ref, n, es.wi);
+    F3 ev = emitter_eval<AREA_MESH>(e, ref, n, es.wi);
     return f3(ev.x / probs, ev.y / probs, ev.z / probs);
+}
+__device__ __forceinline__ F3 emitter_sample(const DScene &S, const DEmitter &e, F3 ref, float sx, float sy,
+                                             ESample &es) {
+    return emitter_sample<false, DScene>(S, S, e, ref, sx, sy, es);
 }
 
 // The lens sample of a camera ray (perspective.cpp:118-122). The reference draws it from one static Independent

@@ -87,6 +87,13 @@ NHD float tri_inv_det(float det) {
     if (__builtin_expect(fabsf(det) >= 0x1p126f, 0)) r = 1.0f / det;
     return r;
 }
+// 1/x of a ray direction component, equal to `1.0f / x` for every x: rcp_rn inside the range it is proven for,
+// |x| in [2^-125, 2^126), and the division outside it (zero, denormal, huge, infinite or NaN components)
+NHD float dir_rcp(float x) {
+    const float a = fabsf(x);
+    if (__builtin_expect(a >= 0x1p-125f && a < 0x1p126f, 1)) return rcp_rn(x);
+    return 1.0f / x;
+}
 
 // Mesh::rayIntersect (mesh.cpp:101-139): edges from the vertices, as the reference computes them
 NHD bool tri_test(float4 a, float4 b, float4 c, F3 o, F3 d, float mint, float maxt, float &t, float &u, float &v) {
@@ -450,7 +457,8 @@ NHD void node_box_tests(const float *nf, F3 o, F3 d, F3 r, float mint, float max
 // (parent inner node << 1) | side: the deferred child's box is tested again when it is
 // popped, with the maxt of that moment -- the reference's visit-time test verbatim.
 // G > 1: the ray is carried by a G-lane group (leaf primitives tested cooperatively, leaf_test_coop).
-template <int DEPTH, bool ORDERED, bool ANY, bool STATS, bool PAIRS = false, int G = 1>
+// RCP: the direction's reciprocals by dir_rcp (the same values as the divisions) instead of three IEEE divisions.
+template <int DEPTH, bool ORDERED, bool ANY, bool STATS, bool PAIRS = false, int G = 1, bool RCP = false>
 NHD bool trace(const Traversal &tv, const DScene &S, F3 o, F3 d, float mint, float maxt, Hit &best, uint32_t *stk,
                int stride, TravStats &st) {
     // adaptive ray epsilon (bvh.cpp:407-410)
@@ -460,7 +468,7 @@ NHD bool trace(const Traversal &tv, const DScene &S, F3 o, F3 d, float mint, flo
     best.k = -1;
     best.t = INFINITY;
     if (S.root_kind == 0 || maxt < mint) return false;
-    const F3 r = f3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+    const F3 r = RCP ? f3(dir_rcp(d.x), dir_rcp(d.y), dir_rcp(d.z)) : f3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
     const bool fin = isfinite(r.x) & isfinite(r.y) & isfinite(r.z);
     bool found = false;
     float near_t;
@@ -558,14 +566,14 @@ NHD bool iso_sphere_hit(const Traversal &tv, int k_prev, F3 o, F3 d, float mint,
 }
 
 // trace (closest hit) of a path's next ray from the surface of primitive k_prev, with the isolated-sphere answer
-template <int DEPTH, bool ORDERED, bool STATS, bool PAIRS = false, int G = 1, bool ISO = true>
+template <int DEPTH, bool ORDERED, bool STATS, bool PAIRS = false, int G = 1, bool ISO = true, bool RCP = false>
 NHD bool trace_next(const Traversal &tv, const DScene &S, int k_prev, F3 o, F3 d, float mint, float maxt, Hit &best,
                     uint32_t *stk, int stride, TravStats &st) {
 #ifndef NH_AB_NO_ISO  // cost attribution builds only: the isolated-sphere test compiled out
     if (ISO && S.iso_spheres && S.root_kind != 0 && iso_sphere_hit<STATS, G>(tv, k_prev, o, d, mint, maxt, best, st))
         return true;
 #endif
-    return trace<DEPTH, ORDERED, false, STATS, PAIRS, G>(tv, S, o, d, mint, maxt, best, stk, stride, st);
+    return trace<DEPTH, ORDERED, false, STATS, PAIRS, G, RCP>(tv, S, o, d, mint, maxt, best, stk, stride, st);
 }
 
 

@@ -165,18 +165,64 @@ __host__ __device__ __forceinline__ int small_pairs_offset_f4(const WfLaunch &L)
     return L.small_nodes + L.small_prims + (L.small_leaves + 1) / 2;
 }
 
+// float4 count of the scene tables of a small scene's LDS image (WfLaunch::small_tab)
+__host__ __device__ __forceinline__ int small_tables_f4(const WfLaunch &L) {
+    return L.small_tab[0] + L.small_tab[1] + L.small_tab[2] + L.small_tab[3] + L.small_tab[4];
+}
+
+// The computed regions of a small scene's LDS image, written by threads tid, tid + nthreads, ...: the
+// pair-interleaved copy of the n primitive records (Traversal::ppairs, kPairF4 float4 per record; the partner of the
+// last record = zeros) and, with frames != null, the flat triangles' shading frames (hit_info reads them instead of
+// a normalize + frame construction per hit). Run once per upload (small_image_kernel): the fused kernels used to run
+// it once per workgroup.
+__device__ __forceinline__ void build_pairs_frames(const float4 *prims_in, int n, float4 *pairs, float4 *frames, int tid,
+                                                   int nthreads) {
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int k = tid; k < n; k += nthreads) {
+        const float4 a = prims_in[3 * k], b = prims_in[3 * k + 1], c = prims_in[3 * k + 2];
+        const bool nx = k + 1 < n;
+        const float4 a1 = nx ? prims_in[3 * k + 3] : z, b1 = nx ? prims_in[3 * k + 4] : z,
+                     c1 = nx ? prims_in[3 * k + 5] : z;
+        float4 *q = pairs + (size_t)kPairF4 * k;
+        // Moller-Trumbore's edges (mesh.cpp:105-106), subtracted once here instead of in every test
+        q[0] = make_float4(a.x, a1.x, a.y, a1.y);
+        q[1] = make_float4(a.z, a1.z, a.w, a1.w);
+        q[2] = make_float4(b.x - a.x, b1.x - a1.x, b.y - a.y, b1.y - a1.y);
+        q[3] = make_float4(b.z - a.z, b1.z - a1.z, c.x - a.x, c1.x - a1.x);
+        q[4] = make_float4(c.y - a.y, c1.y - a1.y, c.z - a.z, c1.z - a1.z);
+        q[5] = make_float4(c.w, c1.w, 0.f, 0.f);
+    }
+    if (frames) {
+        for (int k = tid; k < n; k += nthreads) {
+            const float4 a = prims_in[3 * k], b = prims_in[3 * k + 1], c = prims_in[3 * k + 2];
+            Frame f{};
+            if (prim_is_tri(c)) {
+                const F3 p0 = f3(a.x, a.y, a.z);
+                f = frame_from_n(normalized(cross(sub(f3(b.x, b.y, b.z), p0), sub(f3(c.x, c.y, c.z), p0))));
+            }
+            frames[3 * k] = make_float4(f.s.x, f.s.y, f.s.z, 0.f);
+            frames[3 * k + 1] = make_float4(f.t.x, f.t.y, f.t.z, 0.f);
+            frames[3 * k + 2] = make_float4(f.n.x, f.n.y, f.n.z, 0.f);
+        }
+    }
+}
+
+// float4 count of the dynamic LDS of the fused kernels = of the LDS image they copy: BVH, pair records, scene tables,
+// and the flat triangles' frames (last: left out with small_frames = 0)
+__host__ __device__ __forceinline__ int rr_lds_f4(const WfLaunch &L) {
+    return small_pairs_offset_f4(L) + kPairF4 * (L.small_prims / 3) + small_tables_f4(L) +
+           (L.small_frames ? 3 * (L.small_prims / 3) : 0);
+}
+
 // Stage a small BVH (nodes, leaf table, primitives) into dynamic LDS and return a traversal view
 // of the copy. Instantiated only for SMALL kernels, so every traversal pointer derives from the
 // __shared__ array: the compiler emits ds_read, not flat loads. Called by the whole workgroup.
-// PAIRS: also the pair-interleaved copy of the primitive records (Traversal::ppairs, kPairF4 float4 per
-// record, after the leaf table; record n_prims = zeros).
+// PAIRS (the fused kernels): the whole LDS image of the scene (WfLaunch::small_image: also the pair records, the scene
+// tables and the frames), copied as it stands by all threads -- one round trip, no arithmetic.
 template <bool PAIRS = false>
 __device__ __forceinline__ Traversal stage_small_scene(const Traversal &tv, const WfLaunch &L, float4 *lds) {
     float4 *nodes = lds, *prims = lds + L.small_nodes;
     int2 *leaves = reinterpret_cast<int2 *>(prims + L.small_prims);
-    for (int i = threadIdx.x; i < L.small_nodes; i += blockDim.x) nodes[i] = tv.nodes[i];
-    for (int i = threadIdx.x; i < L.small_prims; i += blockDim.x) prims[i] = tv.prims[i];
-    for (int i = threadIdx.x; i < L.small_leaves; i += blockDim.x) leaves[i] = tv.leaves[i];
     Traversal t;
     t.nodes = nodes;
     t.prims = prims;
@@ -186,48 +232,65 @@ __device__ __forceinline__ Traversal stage_small_scene(const Traversal &tv, cons
     t.wnodes = tv.wnodes;
     t.n_top = 0;
     if constexpr (PAIRS) {
+        // (read through a global address-space pointer: global loads, not flat ones)
+        typedef float NativeF4 __attribute__((ext_vector_type(4)));
+        typedef const __attribute__((address_space(1))) NativeF4 *GlobalF4;
+        const GlobalF4 img = (GlobalF4) reinterpret_cast<const NativeF4 *>(L.small_image);
+        const int n4 = rr_lds_f4(L);
+        for (int i = threadIdx.x; i < n4; i += blockDim.x) {
+            const NativeF4 x = img[i];
+            lds[i] = make_float4(x.x, x.y, x.z, x.w);
+        }
         float4 *pairs = lds + small_pairs_offset_f4(L);
-        const int n = L.small_prims / 3;
-        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int k = threadIdx.x; k < n; k += blockDim.x) {
-            const float4 a = tv.prims[3 * k], b = tv.prims[3 * k + 1], c = tv.prims[3 * k + 2];
-            const bool nx = k + 1 < n;
-            const float4 a1 = nx ? tv.prims[3 * k + 3] : z, b1 = nx ? tv.prims[3 * k + 4] : z,
-                         c1 = nx ? tv.prims[3 * k + 5] : z;
-            float4 *q = pairs + (size_t)kPairF4 * k;
-            // Moller-Trumbore's edges (mesh.cpp:105-106), subtracted once here instead of in every test
-            q[0] = make_float4(a.x, a1.x, a.y, a1.y);
-            q[1] = make_float4(a.z, a1.z, a.w, a1.w);
-            q[2] = make_float4(b.x - a.x, b1.x - a1.x, b.y - a.y, b1.y - a1.y);
-            q[3] = make_float4(b.z - a.z, b1.z - a1.z, c.x - a.x, c1.x - a1.x);
-            q[4] = make_float4(c.y - a.y, c1.y - a1.y, c.z - a.z, c1.z - a1.z);
-            q[5] = make_float4(c.w, c1.w, 0.f, 0.f);
-        }
         t.ppairs = pairs;
-        if (L.small_frames) {  // flat triangles' shading frames (hit_info), from the records just read
-            float4 *fr = pairs + (size_t)kPairF4 * n;
-            for (int k = threadIdx.x; k < n; k += blockDim.x) {
-                const float4 a = tv.prims[3 * k], b = tv.prims[3 * k + 1], c = tv.prims[3 * k + 2];
-                Frame f{};
-                if (prim_is_tri(c)) {
-                    const F3 p0 = f3(a.x, a.y, a.z);
-                    f = frame_from_n(normalized(cross(sub(f3(b.x, b.y, b.z), p0), sub(f3(c.x, c.y, c.z), p0))));
-                }
-                fr[3 * k] = make_float4(f.s.x, f.s.y, f.s.z, 0.f);
-                fr[3 * k + 1] = make_float4(f.t.x, f.t.y, f.t.z, 0.f);
-                fr[3 * k + 2] = make_float4(f.n.x, f.n.y, f.n.z, 0.f);
-            }
-            t.frames = fr;
-        }
+        if (L.small_frames) t.frames = pairs + kPairF4 * (L.small_prims / 3) + small_tables_f4(L);
+    } else {
+        for (int i = threadIdx.x; i < L.small_nodes; i += blockDim.x) nodes[i] = tv.nodes[i];
+        for (int i = threadIdx.x; i < L.small_prims; i += blockDim.x) prims[i] = tv.prims[i];
+        for (int i = threadIdx.x; i < L.small_leaves; i += blockDim.x) leaves[i] = tv.leaves[i];
     }
     __syncthreads();
     return t;
 }
 
-// float4 count of the dynamic LDS of the fused kernels: BVH + pair records + the flat triangles' frames
-__host__ __device__ __forceinline__ int rr_lds_f4(const WfLaunch &L) {
-    return small_pairs_offset_f4(L) + kPairF4 * (L.small_prims / 3) + (L.small_frames ? 3 * (L.small_prims / 3) : 0);
+// The scene tables a shade step reads. DScene has these members itself, so the general kernels pass their DScene;
+// the diffuse area-light kernels pass this view of the LDS image's table regions (pointers derived from the
+// __shared__ array: ds_read). In the image's shape records pdf_off indexes the image's packed CDFs.
+struct SceneTables {
+    const DShape *shapes;
+    const DBsdf *bsdfs;
+    const DEmitter *emitters;
+    const float *area_cdf;
+    const float4 *emit_faces;
+};
+__device__ __forceinline__ SceneTables staged_tables(const WfLaunch &L, float4 *lds) {
+    float4 *p = lds + small_pairs_offset_f4(L) + kPairF4 * (L.small_prims / 3);
+    SceneTables T;
+    T.shapes = reinterpret_cast<const DShape *>(p);
+    p += L.small_tab[0];
+    T.bsdfs = reinterpret_cast<const DBsdf *>(p);
+    p += L.small_tab[1];
+    T.emitters = reinterpret_cast<const DEmitter *>(p);
+    p += L.small_tab[2];
+    T.area_cdf = reinterpret_cast<const float *>(p);
+    p += L.small_tab[3];
+    T.emit_faces = p;
+    return T;
 }
+// the tables a kernel's shade steps read: the staged copies (the diffuse area-light kernels) or S's own
+template <bool STAGED>
+__device__ __forceinline__ decltype(auto) scene_tables(const DScene &S, const WfLaunch &L, float4 *lds) {
+    if constexpr (STAGED) return staged_tables(L, lds);
+    else return (S);
+}
+// A/B builds of the diffuse area-light kernels (-DNH_TRAIT_TABLES=0: tables read from global memory;
+// -DNH_TRAIT_SPLIT=0: one instantiation for bounce 0 and the later bounces)
+#ifndef NH_TRAIT_TABLES
+#define NH_TRAIT_TABLES 1
+#endif
+#ifndef NH_TRAIT_SPLIT
+#define NH_TRAIT_SPLIT 1
+#endif
 
 template <bool SMALL>
 __device__ __forceinline__ Traversal traversal_view(const Traversal &tv, const WfLaunch &L, float4 *lds) {
@@ -595,20 +658,23 @@ struct PathV {
 // or the hit's emitter term, then Russian roulette. Returns whether the path survives; its = the hit's
 // Intersection. The previous bounce's pending light sample (F_NEE) must be resolved already. NMAP: hit_info's normal
 // maps (false only in the lean bounce kernel, for scenes without textures).
-template <bool NMAP = true>
-__device__ __forceinline__ bool shade_head(const DScene &S, const Traversal &tv, PathV &v, const Hit &h, bool found,
-                                           float pdfmat, Its &its) {
+// TRAIT (the diffuse area-light instantiations, see wf_bounce_rr): path_mis with area lights on meshes only -- no
+// path_mats copy, no environment term, no emitter type dispatch; the same operations on the path that is left.
+// T: the scene tables (S, or the staged copies: SceneTables)
+template <bool NMAP = true, bool TRAIT = false, class ST = DScene>
+__device__ __forceinline__ bool shade_head(const DScene &S, const ST &T, const Traversal &tv, PathV &v, const Hit &h,
+                                           bool found, float pdfmat, Its &its) {
     bool have_its = false;
-    if (S.integrator == 1) {  // ---------------- path_mats (path_mats.cpp:16-78)
+    if (!TRAIT && S.integrator == 1) {  // ---------------- path_mats (path_mats.cpp:16-78)
         if (!found) {  // path_mats.cpp:26-35
             if (S.envmap >= 0) v.li = add(v.li, mulc(v.t, env_eval(S, v.d)));
             return false;
         }
-        hit_info<NMAP>(S, tv, h, v.org, v.d, its);
-        const DShape shape = S.shapes[its.shape];
+        hit_info<NMAP>(S, T.shapes, tv, h, v.org, v.d, its);
+        const DShape shape = T.shapes[its.shape];
         if (shape.emitter >= 0) {
             const F3 wi = normalized(sub(its.p, v.org));
-            v.li = add(v.li, mulc(v.t, emitter_eval(S.emitters[shape.emitter], v.org, its.sh.n, wi)));
+            v.li = add(v.li, mulc(v.t, emitter_eval(T.emitters[shape.emitter], v.org, its.sh.n, wi)));
         }
         int counter = (v.flags >> 4) & 3;
         const float succ = e_min(max_coeff(v.t), 0.99f);
@@ -623,26 +689,27 @@ __device__ __forceinline__ bool shade_head(const DScene &S, const Traversal &tv,
     if (!(v.flags & F_FIRST)) {  // finish the previous bounce (path_mis.cpp:115-140)
         // the MIS probe hit an emitter (:117-133): w_mats from the pdfs of both strategies
         if (!(v.flags & F_ZERO_COL) && found) {
-            hit_info<NMAP>(S, tv, h, v.org, v.d, its);
+            hit_info<NMAP>(S, T.shapes, tv, h, v.org, v.d, its);
             have_its = true;
-            const int hem = S.shapes[its.shape].emitter;
+            const int hem = T.shapes[its.shape].emitter;
             if (hem >= 0) {
                 const F3 wim = normalized(sub(its.p, v.org));
-                const float pdfmat_ems = emitter_pdf(S, S.emitters[hem], v.org, its.p, its.sh.n, wim) / n_lights;
+                const float pdfmat_ems =
+                    emitter_pdf<TRAIT>(S, T.shapes, T.emitters[hem], v.org, its.p, its.sh.n, wim) / n_lights;
                 if ((pdfmat + pdfmat_ems) > kEps) v.w_mats = pdfmat / (pdfmat + pdfmat_ems);
             }
         }
         if (v.flags & F_DISCRETE) v.w_mats = 1.f;  // :136-140
     }
     if (!found) {  // path_mis.cpp:32-44: escaped rays see the environment map, no MIS weight
-        if (S.envmap >= 0) v.li = add(v.li, mulc(v.t, env_eval(S, v.d)));
+        if (!TRAIT && S.envmap >= 0) v.li = add(v.li, mulc(v.t, env_eval(S, v.d)));
         return false;
     }
-    if (!have_its) hit_info<NMAP>(S, tv, h, v.org, v.d, its);
-    const DShape shape = S.shapes[its.shape];
+    if (!have_its) hit_info<NMAP>(S, T.shapes, tv, h, v.org, v.d, its);
+    const DShape shape = T.shapes[its.shape];
     if (shape.emitter >= 0) {  // path_mis.cpp:51-56, ref = ray origin
         const F3 wi = normalized(sub(its.p, v.org));
-        v.li = add(v.li, mulc(scl(v.w_mats, v.t), emitter_eval(S.emitters[shape.emitter], v.org, its.sh.n, wi)));
+        v.li = add(v.li, mulc(scl(v.w_mats, v.t), emitter_eval<TRAIT>(T.emitters[shape.emitter], v.org, its.sh.n, wi)));
     }
     float succ = e_min(max_coeff(v.t), 0.99f);  // RR from depth 0 (path_mis.cpp:58-71)
     succ = e_max(succ, kEps);
@@ -657,14 +724,18 @@ __device__ __forceinline__ bool shade_head(const DScene &S, const Traversal &tv,
 // FULL = false (scenes with no mirror / dielectric BSDF and no albedo texture): the light-sample skip and the texture
 // lookup compiled out (rr_step also drops the isolated-sphere test) -- their branches cost C2's bounce kernel ~1 %
 // though they never fire there (profiles/round4_session14_16_c2_ab.txt)
-template <bool FULL = true>
-__device__ __forceinline__ void shade_body(const DScene &S, const Traversal &tv, PathV &v, const Its &its, PState &o,
-                                           bool &nee, float4 &so, float4 &sd) {
-    const DShape shape = S.shapes[its.shape];
-    const DBsdf bsdf = S.bsdfs[shape.bsdf];
+// TRAIT: every BSDF is diffuse and every light an area light on a mesh with an emit_faces record (decided at upload),
+// so the BSDF and emitter type dispatches, the path_mats copy and the other lights' samples are compiled out
+template <bool FULL = true, bool TRAIT = false, class ST = DScene>
+__device__ __forceinline__ void shade_body(const DScene &S, const ST &T, const Traversal &tv, PathV &v, const Its &its,
+                                           PState &o, bool &nee, float4 &so, float4 &sd) {
+    static_assert(!(TRAIT && FULL), "the trait body is a lean body");
+    const DShape shape = T.shapes[its.shape];
+    DBsdf bsdf = T.bsdfs[shape.bsdf];
+    if constexpr (TRAIT) bsdf.type = BSDF_DIFFUSE;  // what the record holds: known to the compiler here
     const F3 alb = FULL ? bsdf_albedo(S, bsdf, its.u, its.v) : f3(bsdf.ar, bsdf.ag, bsdf.ab);
     nee = false;
-    if (S.integrator == 1) {  // path_mats: BSDF sample only
+    if (!TRAIT && S.integrator == 1) {  // path_mats: BSDF sample only
         const float bx = v.rng.next1d(), by = v.rng.next1d();
         F3 wo;
         int measure;
@@ -697,9 +768,9 @@ __device__ __forceinline__ void shade_body(const DScene &S, const Traversal &tv,
         float pdfems = 0.f, pdfems_mats = 0.f;
         if (!skip_nee) {
             const int ei = emitter_pick(S, e0);
-            const DEmitter em = S.emitters[ei];
+            const DEmitter em = T.emitters[ei];
             ESample es;
-            const F3 ems_col = emitter_sample(S, em, its.p, ex, ey, es);
+            const F3 ems_col = emitter_sample<TRAIT>(S, T, em, its.p, ex, ey, es);
             nee = !is_zero(ems_col);
             if (nee) {
                 const F3 we = to_local(its.sh, es.wi);
@@ -708,7 +779,7 @@ __device__ __forceinline__ void shade_body(const DScene &S, const Traversal &tv,
                 li_ems = f3(ems_col.x * cs * f.x * n_lights, ems_col.y * cs * f.y * n_lights,
                             ems_col.z * cs * f.z * n_lights);
                 pdfems_mats = bsdf_pdf(bsdf, wi_l, we, M_SOLID_ANGLE);
-                pdfems = emitter_pdf(S, em, its.p, es.p, es.n, es.wi) / n_lights;
+                pdfems = emitter_pdf<TRAIT>(S, T.shapes, em, its.p, es.p, es.n, es.wi) / n_lights;
                 so = make_float4(es.so.x, es.so.y, es.so.z, es.smint);
                 sd = make_float4(es.sd.x, es.sd.y, es.sd.z, es.smaxt);
             }
@@ -826,11 +897,11 @@ __device__ __forceinline__ bool shade_path(const DScene &S, const Traversal &tv,
         }
     }
     Its its;
-    if (!shade_head<NMAP>(S, tv, v, h, found, ro.w, its)) {
+    if (!shade_head<NMAP>(S, S, tv, v, h, found, ro.w, its)) {
         write_radiance(L, v);
         return false;
     }
-    shade_body(S, tv, v, its, o, nee, so, sd);
+    shade_body(S, S, tv, v, its, o, nee, so, sd);
     return true;
 }
 
@@ -1063,11 +1134,28 @@ __device__ __forceinline__ void store_post_head(const WfBuf &B, int s, const Pat
     B.hit[s] = make_float4(h.t, h.u, h.v, __int_as_float(h.k));
 }
 
-template <bool NMAP = true>
-__device__ __forceinline__ void load_post_head(const DScene &S, const Traversal &tv, const WfLaunch &L, const WfBuf &B,
-                                               int s, PathV &v, Hit &h, Its &its) {
-    const float4 ro = B.ray_o[s], rd = B.ray_d[s], li4 = B.li[s], th4 = B.thr[s], hv = B.hit[s];
-    v.rng.state = B.rng[s];
+// the six stored words of a live path (store_post_head), as loaded
+struct RawState {
+    float4 ro, rd, li4, th4, hv;
+    uint64_t rng;
+};
+__device__ __forceinline__ RawState load_raw_state(const WfBuf &B, int s) {
+    RawState r;
+    r.ro = B.ray_o[s];
+    r.rd = B.ray_d[s];
+    r.li4 = B.li[s];
+    r.th4 = B.thr[s];
+    r.hv = B.hit[s];
+    r.rng = B.rng[s];
+    return r;
+}
+
+// the path a RawState holds and its hit's Intersection (tv: the traversal view hit_info reads the records from)
+template <bool NMAP = true, class ST = DScene>
+__device__ __forceinline__ void unpack_post_head(const DScene &S, const ST &T, const Traversal &tv, const WfLaunch &L,
+                                                 const RawState &r, PathV &v, Hit &h, Its &its) {
+    const float4 ro = r.ro, rd = r.rd, li4 = r.li4, th4 = r.th4, hv = r.hv;
+    v.rng.state = r.rng;
     const int bits = __float_as_int(rd.w);
     v.flags = (int)((unsigned)bits >> kPidBits);
     v.pid = bits & ((1 << kPidBits) - 1);
@@ -1082,17 +1170,24 @@ __device__ __forceinline__ void load_post_head(const DScene &S, const Traversal 
     h.u = hv.y;
     h.v = hv.z;
     h.k = __float_as_int(hv.w);
-    hit_info<NMAP>(S, tv, h, v.org, v.d, its);
+    hit_info<NMAP>(S, T.shapes, tv, h, v.org, v.d, its);
+}
+
+template <bool NMAP = true, class ST = DScene>
+__device__ __forceinline__ void load_post_head(const DScene &S, const ST &T, const Traversal &tv, const WfLaunch &L,
+                                               const WfBuf &B, int s, PathV &v, Hit &h, Its &its) {
+    unpack_post_head<NMAP>(S, T, tv, L, load_raw_state(B, s), v, h, its);
 }
 
 // the camera path of queue entry s at bounce 0, up to its first vertex's head
-template <bool ORDERED, bool STATS, bool NMAP = true>
-__device__ __forceinline__ bool first_vertex(const DScene &S, const Traversal &tv, const WfLaunch &L, int s, PathV &v,
-                                             Hit &h, Its &its, uint32_t *stk, int stride, TravStats &st_e,
+// TRAIT: pinhole camera, trait head (shade_head)
+template <bool ORDERED, bool STATS, bool NMAP = true, bool TRAIT = false, class ST = DScene>
+__device__ __forceinline__ bool first_vertex(const DScene &S, const ST &T, const Traversal &tv, const WfLaunch &L, int s,
+                                             PathV &v, Hit &h, Its &its, uint32_t *stk, int stride, TravStats &st_e,
                                              unsigned long long &q_e) {
     float4 ro, rd;
     float jx, jy;
-    camera_sample(S, L, s, v.rng, ro, rd, jx, jy);
+    camera_sample<!TRAIT>(S, L, s, v.rng, ro, rd, jx, jy);
     if (L.jit) L.jit[s] = make_float2(jx, jy);
     v.org = xyz(ro);
     v.d = xyz(rd);
@@ -1104,8 +1199,9 @@ __device__ __forceinline__ bool first_vertex(const DScene &S, const Traversal &t
     v.pid = s;
     const bool live = rd.w >= ro.w;
     q_e += live ? 1 : 0;
-    const bool found = live && trace<16, ORDERED, false, STATS, true>(tv, S, v.org, v.d, ro.w, rd.w, h, stk, stride, st_e);
-    if (!shade_head<NMAP>(S, tv, v, h, found, 0.f, its)) {
+    const bool found =
+        live && trace<16, ORDERED, false, STATS, true, 1, TRAIT>(tv, S, v.org, v.d, ro.w, rd.w, h, stk, stride, st_e);
+    if (!shade_head<NMAP, TRAIT>(S, T, tv, v, h, found, 0.f, its)) {
         write_radiance(L, v);
         return false;
     }
@@ -1125,8 +1221,11 @@ struct TailClocks {
 // group (every lane the same state and arithmetic; leaf primitives tested cooperatively; one lane writes and counts).
 // NMAP: hit_info's normal maps (FULL kernels of scenes without normal maps compile them out: the inlined normal-map
 // branches and their tex_eval calls cost C1 / C4 2.5 % when present, profiles/round6_ab_nmap.txt)
-template <bool ORDERED, bool STATS, bool CLK = false, int G = 1, bool FULL = true, bool NMAP = FULL>
-__device__ __forceinline__ bool rr_step(const DScene &S, const Traversal &tv, const WfLaunch &L, PathV &v, Its &its,
+// TRAIT: the diffuse area-light body and head; the stream increment stays in its registers over the step instead of
+// being re-derived from the path id (path_of), and the traversals take the guarded fast reciprocal (trace<.., RCP>)
+template <bool ORDERED, bool STATS, bool CLK = false, int G = 1, bool FULL = true, bool NMAP = FULL, bool TRAIT = false,
+          class ST = DScene>
+__device__ __forceinline__ bool rr_step(const DScene &S, const ST &T, const Traversal &tv, const WfLaunch &L, PathV &v, Its &its,
                                         Hit &h, uint32_t *stk, int stride, TravStats &st_e, TravStats &st_s,
                                         unsigned long long &q_e, unsigned long long &q_s, TailClocks *clk = nullptr) {
     const bool lead = G == 1 || (threadIdx.x & (G - 1)) == 0;
@@ -1136,7 +1235,8 @@ __device__ __forceinline__ bool rr_step(const DScene &S, const Traversal &tv, co
     unsigned long long t0 = 0, t1 = 0;
     unsigned long long *cs = CLK ? (G > 1 ? clk->cc : clk->c) : nullptr;
     if constexpr (CLK) t0 = clock64();
-    shade_body<FULL>(S, tv, v, its, o, nee, so, sd);
+    [[maybe_unused]] const uint64_t inc = v.rng.inc;
+    shade_body<FULL, TRAIT>(S, T, tv, v, its, o, nee, so, sd);
     if constexpr (CLK) {
         t1 = clock64();
         if (lead) cs[0] += t1 - t0;
@@ -1145,7 +1245,7 @@ __device__ __forceinline__ bool rr_step(const DScene &S, const Traversal &tv, co
     if (nee) {  // the light sample's any-hit query, its outcome applied as the next shade_path would
         Hit hs;
         if (lead) ++q_s;
-        if (!trace<16, ORDERED, true, STATS, true, G>(tv, S, xyz(so), xyz(sd), so.w, sd.w, hs, stk, stride, st_s)) {
+        if (!trace<16, ORDERED, true, STATS, true, G, TRAIT>(tv, S, xyz(so), xyz(sd), so.w, sd.w, hs, stk, stride, st_s)) {
             o.li.x = o.li.x + o.pe.x;
             o.li.y = o.li.y + o.pe.y;
             o.li.z = o.li.z + o.pe.z;
@@ -1164,15 +1264,28 @@ __device__ __forceinline__ bool rr_step(const DScene &S, const Traversal &tv, co
     }
     const bool live = o.rd.w >= o.ro.w;
     if (lead) q_e += live ? 1 : 0;
-    const bool found = live && trace_next<16, ORDERED, STATS, true, G, FULL>(tv, S, h.k, xyz(o.ro), xyz(o.rd), o.ro.w,
-                                                                      o.rd.w, h, stk, stride, st_e);
+    const bool found = live && trace_next<16, ORDERED, STATS, true, G, FULL, TRAIT>(tv, S, h.k, xyz(o.ro), xyz(o.rd),
+                                                                             o.ro.w, o.rd.w, h, stk, stride, st_e);
     if constexpr (CLK) {
         t1 = clock64();
         if (lead) cs[2] += t1 - t0;
         t0 = t1;
     }
-    v = path_of(L, o);
-    const bool alive = shade_head<NMAP>(S, tv, v, h, found, o.pdfmat, its);
+    if constexpr (TRAIT) {  // path_of with the path's own stream increment (the same value: pid does not change)
+        v.org = xyz(o.ro);
+        v.d = xyz(o.rd);
+        v.li = xyz(o.li);
+        v.w_mats = o.li.w;
+        v.t = xyz(o.thr);
+        v.w_ems = o.thr.w;
+        v.rng.state = o.rng;
+        v.rng.inc = inc;
+        v.flags = o.flags;
+        v.pid = o.pid;
+    } else {
+        v = path_of(L, o);
+    }
+    const bool alive = shade_head<NMAP, TRAIT>(S, T, tv, v, h, found, o.pdfmat, its);
     if constexpr (CLK) {
         if (lead) cs[3] += clock64() - t0;
         if (lead) ++(G > 1 ? clk->coop_bounces : clk->bounces);
@@ -1191,24 +1304,35 @@ __device__ __forceinline__ bool rr_step(const DScene &S, const Traversal &tv, co
 
 // one queue entry of a RR-ahead bounce: load its path (or, at bounce 0, its camera ray and first hit) and run
 // rr_step; true when the path lives on (v, h: its state to store)
-template <bool ORDERED, bool STATS, bool FULL, bool NMAP = FULL>
-__device__ __forceinline__ bool bounce_path(const DScene &S, const Traversal &tv, const WfLaunch &L, const QView &qv,
+// BOUNCE: -1 bounce 0 or a later one, by L.first; 0 / 1 the kernel runs only bounce 0 / only later bounces, so the other
+// entry's code (camera sample and first closest hit, or the state unpacking) is not compiled in. pre: the path's
+// stored words when the kernel loaded them ahead of its staging barrier (BOUNCE = 1), else null.
+template <bool ORDERED, bool STATS, bool FULL, bool NMAP = FULL, bool TRAIT = false, int BOUNCE = -1, class ST = DScene>
+__device__ __forceinline__ bool bounce_path(const DScene &S, const ST &T, const Traversal &tv, const WfLaunch &L, const QView &qv,
                                             int q, uint32_t *my_stk, PathV &v, Hit &h, TravStats &st_e,
                                             TravStats &st_s, unsigned long long &q_e, unsigned long long &q_s,
-                                            TailClocks &clk, unsigned long long &c_load) {
-    const int s = queue_slot(qv.pre, L.seg_cap, q);
+                                            TailClocks &clk, unsigned long long &c_load, const RawState *pre = nullptr) {
     Its its;
     bool alive = true;
     unsigned long long t_ph = 0;
     if constexpr (STATS) t_ph = clock64();
-    if (L.first) alive = first_vertex<ORDERED, STATS, NMAP>(S, tv, L, s, v, h, its, my_stk, NH_BOUNCE_TB, st_e, q_e);
-    else load_post_head<NMAP>(S, tv, L, L.st.buf[L.in_q], s, v, h, its);
+    const bool first = BOUNCE < 0 ? L.first != 0 : BOUNCE == 0;
+    if (first) {
+        const int s = queue_slot(qv.pre, L.seg_cap, q);
+        alive = first_vertex<ORDERED, STATS, NMAP, TRAIT>(S, T, tv, L, s, v, h, its, my_stk, NH_BOUNCE_TB, st_e, q_e);
+    } else if (BOUNCE == 1) {
+        unpack_post_head<NMAP>(S, T, tv, L, *pre, v, h, its);
+    } else {
+        load_post_head<NMAP>(S, T, tv, L, L.st.buf[L.in_q], queue_slot(qv.pre, L.seg_cap, q), v, h, its);
+    }
     if constexpr (STATS) c_load += clock64() - t_ph;
-    return alive && rr_step<ORDERED, STATS, STATS, 1, FULL, NMAP>(S, tv, L, v, its, h, my_stk, NH_BOUNCE_TB, st_e, st_s, q_e,
-                                                            q_s, &clk);
+    return alive && rr_step<ORDERED, STATS, STATS, 1, FULL, NMAP, TRAIT>(S, T, tv, L, v, its, h, my_stk, NH_BOUNCE_TB,
+                                                                   st_e, st_s, q_e, q_s, &clk);
 }
 
-template <bool ORDERED, bool STATS, bool SORT, bool FULL = true, bool NMAP = FULL>
+// TRAIT, BOUNCE: the diffuse area-light instantiations (launch_wf_bounce_trait), one for bounce 0 and one for the later
+// bounces; the later-bounce kernel issues its path's state loads before the staging barrier and uses them after it
+template <bool ORDERED, bool STATS, bool SORT, bool FULL = true, bool NMAP = FULL, bool TRAIT = false, int BOUNCE = -1>
 __global__ __launch_bounds__(NH_BOUNCE_TB, NH_BOUNCE_WAVES) void wf_bounce_rr(const DScene *__restrict__ Sp, Traversal tv_g,
                                                                      WfLaunch L) {
     __shared__ uint32_t stk[16 * NH_BOUNCE_TB];
@@ -1219,9 +1343,12 @@ __global__ __launch_bounds__(NH_BOUNCE_TB, NH_BOUNCE_WAVES) void wf_bounce_rr(co
     if (base >= qv.n) return;  // whole workgroup
     if (threadIdx.x < kMatClasses) s_n[threadIdx.x] = 0u;  // visible after the staging barrier
     const DScene &S = *Sp;
+    const int q = base + (int)threadIdx.x;
+    [[maybe_unused]] RawState pre;
+    if constexpr (BOUNCE == 1)
+        if (q < qv.n) pre = load_raw_state(L.st.buf[L.in_q], queue_slot(qv.pre, L.seg_cap, q));
     const Traversal tv = stage_small_scene<true>(tv_g, L, lds_scene);
     const int shard = blockIdx.x & (kQueueShards - 1);
-    const int q = base + (int)threadIdx.x;
     uint32_t *my_stk = stk + threadIdx.x;
     TravStats st_e{0, 0, 0}, st_s{0, 0, 0};
     unsigned long long q_e = 0, q_s = 0;
@@ -1234,7 +1361,9 @@ __global__ __launch_bounds__(NH_BOUNCE_TB, NH_BOUNCE_WAVES) void wf_bounce_rr(co
     TailClocks clk;
     unsigned long long c_load = 0, c_store = 0, t_ph = 0;
     if (q < qv.n) {
-        cont = bounce_path<ORDERED, STATS, FULL, NMAP>(S, tv, L, qv, q, my_stk, v, h, st_e, st_s, q_e, q_s, clk, c_load);
+        const auto &T = scene_tables<TRAIT && NH_TRAIT_TABLES>(S, L, lds_scene);
+        cont = bounce_path<ORDERED, STATS, FULL, NMAP, TRAIT, BOUNCE>(S, T, tv, L, qv, q, my_stk, v, h, st_e, st_s, q_e, q_s,
+                                                                      clk, c_load, BOUNCE == 1 ? &pre : nullptr);
         if (cont) cls = prim_material(tv.prims[3 * h.k + 2]);  // a live path's ray has hit something
         if constexpr (STATS) t_ph = clock64();
     }
@@ -1285,7 +1414,8 @@ __global__ __launch_bounds__(NH_BOUNCE_TB, NH_BOUNCE_WAVES) void wf_bounce_rr(co
 // the other. Only which lanes run which operation changes; every path's operations and draws are the same.
 constexpr int kTailCoopWords = 48;  // 32-bit words of one handed-over path (PathV, Hit, Its, bounce count)
 // FULL = false: the lean body of wf_bounce_rr<.., FULL = false> (scenes with no mirror / dielectric BSDF and no texture)
-template <bool ORDERED, bool STATS, int TB, int W, bool FULL = true, bool NMAP = FULL>
+// TRAIT: the diffuse area-light body and head (as wf_bounce_rr<.., TRAIT>)
+template <bool ORDERED, bool STATS, int TB, int W, bool FULL = true, bool NMAP = FULL, bool TRAIT = false>
 __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(W))) void wf_tail_rr(
     const DScene *__restrict__ Sp, Traversal tv_g, WfLaunch L, int coop) {
     __shared__ uint32_t stk[16 * TB];
@@ -1305,14 +1435,15 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(W))) void wf
     Hit h;
     Its its;
     unsigned long long nb = 0;  // bounces of this lane's path
-    if (alive) load_post_head<NMAP>(S, tv, L, B, queue_slot(qv.pre, L.seg_cap, q), v, h, its);
+    const auto &T = scene_tables<TRAIT && NH_TRAIT_TABLES>(S, L, lds_scene);
+    if (alive) load_post_head<NMAP>(S, T, tv, L, B, queue_slot(qv.pre, L.seg_cap, q), v, h, its);
     const bool can_coop = TB == 64 && coop == 16;
     for (;;) {
         const unsigned long long m = __ballot(alive);
         if (m == 0ull || (can_coop && __popcll(m) <= 4)) break;
         if (alive) {
-            alive = rr_step<ORDERED, STATS, STATS, 1, FULL, NMAP>(S, tv, L, v, its, h, stk + threadIdx.x, TB, st_e, st_s,
-                                                            q_e, q_s, &clk);
+            alive = rr_step<ORDERED, STATS, STATS, 1, FULL, NMAP, TRAIT>(S, T, tv, L, v, its, h, stk + threadIdx.x, TB, st_e,
+                                                                   st_s, q_e, q_s, &clk);
             ++nb;
         }
     }
@@ -1342,8 +1473,8 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(W))) void wf
             }
             while (__ballot(carry)) {
                 if (carry) {
-                    carry = rr_step<ORDERED, STATS, STATS, 16, FULL, NMAP>(S, tv, L, v, its, h, stk + threadIdx.x, TB, st_e,
-                                                                    st_s, q_e, q_s, &clk);
+                    carry = rr_step<ORDERED, STATS, STATS, 16, FULL, NMAP, TRAIT>(S, T, tv, L, v, its, h, stk + threadIdx.x,
+                                                                            TB, st_e, st_s, q_e, q_s, &clk);
                     ++nb;
                 }
             }
@@ -1405,6 +1536,11 @@ __global__ __launch_bounds__(256) void wf_camera_rays(const DScene *__restrict__
         B.ray_o[s] = ro;
         B.ray_d[s] = rd;
     }
+}
+
+// the computed regions of a small scene's LDS image, once per upload (nh_api.hip build_small_image)
+__global__ __launch_bounds__(256) void small_image_kernel(const float4 *prims, int n, float4 *pairs, float4 *frames) {
+    build_pairs_frames(prims, n, pairs, frames, (int)threadIdx.x, 256);
 }
 
 __global__ __launch_bounds__(256) void wf_pack_rr(WfLaunch L, WfBuf dst, unsigned *dst_counts) {
@@ -1629,7 +1765,8 @@ void launch_wf_bounce(const DScene *S, const Traversal &tv, const WfLaunch &L, b
 
 #if NH_WF_HAS_PART(2)
 void launch_wf_bounce_rr(const DScene *S, const Traversal &tv, const WfLaunch &L, bool ordered, bool stats, bool sort,
-                         bool lean, bool nmap, int bound, hipStream_t st) {
+                         bool lean, bool nmap, bool trait, int bound, hipStream_t st) {
+    if (trait && ordered && lean && !sort) return launch_wf_bounce_trait(S, tv, L, stats, bound, st);
     int blocks = std::max(1, (bound + NH_BOUNCE_TB - 1) / NH_BOUNCE_TB);
     blocks = (blocks + kQueueShards - 1) / kQueueShards * kQueueShards;
     const size_t lds = 16 * (size_t)rr_lds_f4(L);
@@ -1655,7 +1792,7 @@ void launch_wf_bounce_rr(const DScene *S, const Traversal &tv, const WfLaunch &L
 }
 
 void launch_wf_tail_rr(const DScene *S, const Traversal &tv, const WfLaunch &L, bool ordered, bool stats, int bound,
-                       bool specular, bool lean, bool nmap, hipStream_t st) {
+                       bool specular, bool lean, bool nmap, bool trait, hipStream_t st) {
     const char *e = std::getenv("NH_TAIL_WG");  // threads per tail workgroup: 64 (default) or 256
     const int tb = e && std::atoi(e) == 256 ? 256 : 64;
     // register budget, NH_TAIL_RR_WAVES=1|2|4: by default 1 wave/SIMD for scenes with mirror / dielectric BSDFs (their
@@ -1668,6 +1805,8 @@ void launch_wf_tail_rr(const DScene *S, const Traversal &tv, const WfLaunch &L, 
     if (ln && ln[0] == '0') lean = false;
     const char *cp = std::getenv("NH_TAIL_COOP");  // lanes per path once <= 4 remain in a wave: 16 (default) or 1
     const int coop = cp && std::atoi(cp) == 1 ? 1 : 16;
+    // the trait tail exists at the default shape only: 64 threads, 2 waves/SIMD, lean body
+    if (trait && ordered && lean && tb == 64 && waves == 2) return launch_wf_tail_trait(S, tv, L, stats, bound, coop, st);
     // one path per lane: the grid covers the bound (tail bounds are <= kTailCap paths)
     const dim3 grid(std::max(1, (bound + tb - 1) / tb));
     const size_t lds = 16 * (size_t)rr_lds_f4(L);
@@ -1690,6 +1829,32 @@ void launch_wf_tail_rr(const DScene *S, const Traversal &tv, const WfLaunch &L, 
 
 #endif
 
+#if NH_WF_HAS_PART(4)
+void launch_wf_bounce_trait(const DScene *S, const Traversal &tv, const WfLaunch &L, bool stats, int bound,
+                            hipStream_t st) {
+    int blocks = std::max(1, (bound + NH_BOUNCE_TB - 1) / NH_BOUNCE_TB);
+    blocks = (blocks + kQueueShards - 1) / kQueueShards * kQueueShards;
+    const size_t lds = 16 * (size_t)rr_lds_f4(L);
+#define NH_FBT(T, B) \
+    hipLaunchKernelGGL((wf_bounce_rr<true, T, false, false, false, true, B>), dim3(blocks), dim3(NH_BOUNCE_TB), lds, st, S, tv, L)
+#if NH_TRAIT_SPLIT
+    if (L.first) { if (stats) NH_FBT(true, 0); else NH_FBT(false, 0); }
+    else { if (stats) NH_FBT(true, 1); else NH_FBT(false, 1); }
+#else
+    if (stats) NH_FBT(true, -1); else NH_FBT(false, -1);
+#endif
+#undef NH_FBT
+}
+
+void launch_wf_tail_trait(const DScene *S, const Traversal &tv, const WfLaunch &L, bool stats, int bound, int coop,
+                          hipStream_t st) {
+    const dim3 grid(std::max(1, (bound + 63) / 64));
+    const size_t lds = 16 * (size_t)rr_lds_f4(L);
+    if (stats) hipLaunchKernelGGL((wf_tail_rr<true, true, 64, 2, false, false, true>), grid, dim3(64), lds, st, S, tv, L, coop);
+    else hipLaunchKernelGGL((wf_tail_rr<true, false, 64, 2, false, false, true>), grid, dim3(64), lds, st, S, tv, L, coop);
+}
+#endif
+
 #if NH_WF_HAS_PART(1)
 void launch_wf_camera_rays(const DScene *S, const WfLaunch &L, int bound, hipStream_t st) {
     const int blocks = std::min(std::max(1, (bound + 255) / 256), kTraceBlocksMax);
@@ -1700,6 +1865,11 @@ void launch_wf_camera_rays(const DScene *S, const WfLaunch &L, int bound, hipStr
 #if NH_WF_HAS_PART(1)
 void launch_wf_counts(const unsigned *src, unsigned *host_dst, int n_copy, unsigned *zero, int n_zero, hipStream_t st) {
     hipLaunchKernelGGL(wf_counts_kernel, dim3(1), dim3(256), 0, st, src, host_dst, n_copy, zero, n_zero);
+}
+
+void launch_small_image(const Traversal &tv, int n_prim_f4, int pairs_off, int frames_off, float4 *image, hipStream_t st) {
+    hipLaunchKernelGGL(small_image_kernel, dim3(1), dim3(256), 0, st, tv.prims, n_prim_f4 / 3, image + pairs_off,
+                       frames_off >= 0 ? image + frames_off : nullptr);
 }
 
 void launch_wf_pack_rr(const WfLaunch &L, const WfBuf &dst, unsigned *dst_counts, int bound, hipStream_t st) {

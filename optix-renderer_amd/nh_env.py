@@ -3,7 +3,8 @@
 The wavefront pipeline drives up to three path pools on their own streams; each needs its own hardware queue, or
 one pool's long tail kernel blocks another's bounces (HIP's default is 4 queues per process, one of which the
 context's own stream takes; the MI355X boxes export that 4 explicitly: C1 -15 %, profiles/round4_session3_ab.txt).
-Shared by the binding (`nori_hip`, at import) and `bench.py` (before torch may initialise HIP).
+Shared by the binding (`nori_hip.configure_runtime()`, an explicit call before the first device use: importing
+`nori_hip` changes no environment) and `bench.py` (before torch may initialise HIP).
 """
 import os
 

@@ -35,6 +35,7 @@ INTEGRATOR_PATH_MIS, INTEGRATOR_PATH_MATS, INTEGRATOR_DIRECT_EMS, INTEGRATOR_DIR
 INTEGRATOR_DIRECT = 5  # the point-light `direct` integrator of scenes/pa1 (direct.cpp)
 INTEGRATOR_NORMALS = 6  # the `normals` integrator of the normal-map scenes (normals.cpp)
 MODE_MEGAKERNEL, MODE_WAVEFRONT = 0, 1
+SMALL_TABLES_BYTES = 4096  # NH_SMALL_TABLES_BYTES: LDS budget of the scene tables of the diffuse area-light kernels
 TRAVERSAL_REFERENCE, TRAVERSAL_ORDERED, TRAVERSAL_WIDE = 0, 1, 2
 DENOISER_NONE, DENOISER_SIMPLE = 0, 1
 LENS_DRAWS_LTR, LENS_DRAWS_RTL = 0, 1
@@ -168,7 +169,7 @@ class nh_render_stats(C.Structure):
                                   "tail_coop_cycles_shadow", "tail_coop_cycles_closest", "tail_coop_cycles_head",
                                   "tail_coop_bounces", "bounce_cycles_load", "bounce_cycles_body",
                                   "bounce_cycles_shadow", "bounce_cycles_closest", "bounce_cycles_head",
-                                  "bounce_cycles_store", "bounce_bounces")]
+                                  "bounce_cycles_store", "bounce_bounces", "bounce_traits")]
 
 
 def _sig(name, res, *args):
