@@ -53,7 +53,7 @@ extern "C" {
 /* ---- scene description (flattened Nori scene graph) --------------------- */
 
 enum { NH_SHAPE_MESH = 0, NH_SHAPE_SPHERE = 1 };
-enum { NH_BSDF_DIFFUSE = 0, NH_BSDF_MIRROR = 1, NH_BSDF_DIELECTRIC = 2, NH_BSDF_MICROFACET = 3 };
+enum { NH_BSDF_DIFFUSE = 0, NH_BSDF_MIRROR = 1, NH_BSDF_DIELECTRIC = 2, NH_BSDF_MICROFACET = 3, NH_BSDF_DISNEY = 4 };
 enum { NH_EMITTER_AREA = 0, NH_EMITTER_POINT = 1, NH_EMITTER_ENVMAP = 2 };
 /* path_mis (src/integrators/path_mis.cpp), path_mats (path_mats.cpp), the single-bounce
  * direct_ems / direct_mats / direct_mis (direct_ems.cpp, direct_mats.cpp, direct_mis.cpp), the
@@ -87,16 +87,22 @@ typedef struct nh_shape {
                                 spheres re-derive their frame from shFrame.toWorld(eval(uv)) (sphere.cpp:115-121) */
 } nh_shape;
 
-/* One Nori BSDF (src/bsdf/{diffuse,mirror,dielectric,microfacet}.cpp). */
+/* One Nori BSDF (src/bsdf/{diffuse,mirror,dielectric,microfacet,disney}.cpp). nh_upload_scene rejects a type
+ * outside NH_BSDF_DIFFUSE..NH_BSDF_DISNEY with NH_ERR_INVALID. */
 typedef struct nh_bsdf {
     int32_t type;            /* NH_BSDF_* */
-    float albedo[3];         /* diffuse: constant albedo texture */
+    float albedo[3];         /* diffuse / disney: constant albedo texture */
     float alpha;             /* microfacet: Beckmann roughness */
     float int_ior, ext_ior;  /* dielectric / microfacet */
     float kd[3];             /* microfacet diffuse base */
     float ks;                /* microfacet: 1 - max(kd) */
-    uint32_t albedo_texture; /* diffuse: 1 + index into nh_scene_desc.textures of its Texture<Color3f> albedo
-                                child (diffuse.cpp:70-91); 0 = the constant albedo above */
+    uint32_t albedo_texture; /* diffuse / disney: 1 + index into nh_scene_desc.textures of its Texture<Color3f> albedo
+                                child (diffuse.cpp:70-91, disney.cpp:88-109); 0 = the constant albedo above */
+    /* disney (disney.cpp:32-41), each after the constructor's clamp(.., 0, 1), in this order: metallic [0],
+       subsurface [0], specular [0.5], roughness [0.5], specularTint [0], anisotropic [0], sheen [0], sheenTint [0.5],
+       clearcoat [0], clearcoatGloss [1]. Appended: clients that fill the fields above by name compile unchanged. */
+    float metallic, subsurface, specular, roughness, specular_tint, anisotropic, sheen, sheen_tint, clearcoat,
+          clearcoat_gloss;
 } nh_bsdf;
 
 /* A Texture<Color3f> child of a BSDF, evaluated at the hit's uv (Intersection::uv, BSDFQueryRecord::uv):
@@ -441,6 +447,19 @@ int nh_denoise(nh_ctx *ctx, const nh_denoiser *params);
 /* the same on a caller's host ImageBlock: (width + 2 border) x (height + 2 border) x 4 floats, in place */
 int nh_denoise_image(nh_ctx *ctx, float *rgbw, int32_t width, int32_t height, int32_t border,
                      const nh_denoiser *params);
+/* BSDF queries on the device, by the bsdf_eval / bsdf_pdf / bsdf_sample device functions the render kernels call: the
+ * GPU counterpart of the reference's chi2test / ttest BSDF hooks (src/utils/chi2test.cpp, ttest.cpp). One BSDF of
+ * any NH_BSDF_* type, n queries in its local frame; `albedo` (3 floats, or NULL for bsdf->albedo) stands in for the
+ * albedo texture's value at the query's uv, and bsdf->albedo_texture != 0 makes a Disney BSDF form its colour terms
+ * per query from it (the textured route) instead of once (the constant-albedo route).
+ *   NH_BSDF_QUERY_EVAL    in: wi, wo (3n floats each). out: value = eval(wi, wo) (3n), pdf = pdf(wi, wo) (n), both in
+ *                         the solid-angle measure; wo_out / measure may be NULL
+ *   NH_BSDF_QUERY_SAMPLE  in: wi (3n), sample (2n). out: wo_out (3n), value = the sample's weight (3n), measure (n:
+ *                         0 unknown, 1 solid angle, 2 discrete), pdf = pdf(wi, wo_out) in that measure (n)
+ * Needs no uploaded scene. */
+enum { NH_BSDF_QUERY_EVAL = 0, NH_BSDF_QUERY_SAMPLE = 1 };
+int nh_bsdf_query(nh_ctx *ctx, const nh_bsdf *bsdf, const float *albedo, int32_t mode, int32_t n, const float *wi,
+                  const float *wo, const float *sample, float *wo_out, float *value, float *pdf, int32_t *measure);
 const char *nh_last_error(const nh_ctx *ctx);
 
 #ifdef __cplusplus

@@ -139,8 +139,12 @@ struct nh_ctx {
     int wide_w = 4;      // children per wide node of tv.wnodes: 4, or 8 (NH_WIDE8=1)
     int n_node_f4 = 0, n_leaves = 0, n_prim_f4 = 0;  // GPU BVH sizes (float4 / int2 entries)
     std::vector<uint32_t> bvh_indices, shape_offset;
-    std::vector<int> shape_bsdf_type;  // BSDF type of each shape (material key of the sorted queues)
+    // material key of each shape in the sorted queues (the two kPrimMatShift bits of its primitive records): its BSDF
+    // type, or for a Disney BSDF a key no other BSDF type of the scene uses (nh_upload_scene)
+    std::vector<int> shape_bsdf_type;
+    std::vector<int> shape_bsdf_real;  // NH_BSDF_* of each shape
     int n_bsdf_types = 0;              // distinct BSDF types in the scene
+    bool disney = false;               // a Disney BSDF: the scene renders with the nh_disney:: kernels (NH_LAUNCH)
     bool specular = false;             // a mirror or dielectric BSDF: long discrete chains, long chunk tails
     bool textured = false;             // a BSDF with an albedo texture
     bool normal_mapped = false;        // a shape with a normal map (the full bounce / tail bodies' NMAP instantiation)
@@ -182,6 +186,9 @@ struct nh_ctx {
     uint64_t stats_comm_inits = 0;  // communicator cliques this context created as reduce root
 };
 
+// A launcher of a kernel that shades, from the set nh_upload_scene chose for the context's scene (nh_internal.h)
+#define NH_LAUNCH(c, fn) ((c)->disney ? nh_disney::nh::fn : nh::fn)
+
 extern "C" {
 static void pool_free(WfPool &p);
 static int pipeline_drain(nh_ctx *c);
@@ -218,6 +225,38 @@ int upload(nh_ctx *c, std::vector<void *> &owner, const T *src, size_t n, const 
 void free_all(std::vector<void *> &v) {
     for (void *p : v) (void)hipFree(p);
     v.clear();
+}
+
+// The DDisney side record of a Disney nh_bsdf: its ten parameters (the loader's clamped values); the folded fields
+// are written on the device (disney_upload)
+nhd::DDisney disney_record(const nh_bsdf &b) {
+    nhd::DDisney o;
+    std::memset(&o, 0, sizeof(o));
+    o.metallic = b.metallic; o.subsurface = b.subsurface; o.specular = b.specular; o.roughness = b.roughness;
+    o.specular_tint = b.specular_tint; o.anisotropic = b.anisotropic; o.sheen = b.sheen; o.sheen_tint = b.sheen_tint;
+    o.clearcoat = b.clearcoat; o.clearcoat_gloss = b.clearcoat_gloss;
+    return o;
+}
+// a Disney DBsdf names its side record by address (nh_device.h DBsdf::disney_lo / disney_hi, disney_rec)
+void disney_set_record(nhd::DBsdf &o, const nhd::DDisney *rec) {
+    const uint64_t a = (uint64_t)reinterpret_cast<uintptr_t>(rec);
+    o.disney_lo = (uint32_t)a;
+    o.disney_hi = (uint32_t)(a >> 32);
+}
+// Uploads the side records and folds their constants on the device (nh_disney.hip disney_fold_kernel: everything of
+// Disney::eval that does not depend on the directions, by the device's own float operations -- as cam_o and
+// emit_faces are formed once at upload). albedo: 3 floats per record.
+int disney_upload(nh_ctx *c, std::vector<void *> &owner, const std::vector<nhd::DDisney> &recs,
+                  const std::vector<float> &albedo, nhd::DDisney **out) {
+    const nhd::DDisney *d_recs = nullptr;
+    const float *d_alb = nullptr;
+    if (int rc = upload(c, owner, recs.data(), recs.size(), &d_recs)) return rc;
+    if (int rc = upload(c, owner, albedo.data(), albedo.size(), &d_alb)) return rc;
+    *out = const_cast<nhd::DDisney *>(d_recs);
+    nh_disney::nh::launch_disney_fold(*out, d_alb, (int)recs.size(), c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // (the host vectors are the caller's locals)
+    return NH_OK;
 }
 
 // BlockGenerator spiral order (src/utils/block.cpp:151-199) -> rank per block id
@@ -499,7 +538,8 @@ int nh_upload_scene(nh_ctx *c, const nh_scene_desc *d) {
             return fail(c, "shape normal map index out of range"), NH_ERR_INVALID;
         // bit 0: uv read (textured albedo or normal map); bits 1+: 1 + the normal map's texture index
         o.tex_uv = ((int)s.normal_map << 1) |
-                   ((d->bsdfs[s.bsdf].type == NH_BSDF_DIFFUSE && d->bsdfs[s.bsdf].albedo_texture != 0) || s.normal_map
+                   (((d->bsdfs[s.bsdf].type == NH_BSDF_DIFFUSE || d->bsdfs[s.bsdf].type == NH_BSDF_DISNEY) &&
+                     d->bsdfs[s.bsdf].albedo_texture != 0) || s.normal_map
                         ? 1 : 0);
         o.ef_off = -1;
     }
@@ -520,8 +560,18 @@ int nh_upload_scene(nh_ctx *c, const nh_scene_desc *d) {
             }
         }
     std::vector<DBsdf> db(d->n_bsdfs);
+    // Disney BSDFs: a DDisney side record each (the DBsdf holds its address), and the albedo its constants fold
+    std::vector<nhd::DDisney> dz;
+    std::vector<float> dz_albedo;
+    std::vector<uint32_t> dz_owner;
     for (uint32_t i = 0; i < d->n_bsdfs; ++i) {
         const nh_bsdf &b = d->bsdfs[i];
+        if (b.type < NH_BSDF_DIFFUSE || b.type > NH_BSDF_DISNEY) return fail(c, "unknown BSDF type"), NH_ERR_INVALID;
+        if (b.type == NH_BSDF_DISNEY) {
+            dz.push_back(disney_record(b));
+            dz_albedo.insert(dz_albedo.end(), b.albedo, b.albedo + 3);
+            dz_owner.push_back(i);
+        }
         DBsdf &o = db[i];
         std::memset(&o, 0, sizeof(o));
         o.type = b.type;
@@ -530,7 +580,12 @@ int nh_upload_scene(nh_ctx *c, const nh_scene_desc *d) {
         o.kr = b.kd[0]; o.kg = b.kd[1]; o.kb = b.kd[2];
         if (b.albedo_texture > d->n_textures || (b.albedo_texture && !d->textures))
             return fail(c, "BSDF albedo texture index out of range"), NH_ERR_INVALID;
-        o.tex = b.type == NH_BSDF_DIFFUSE ? (int)b.albedo_texture : 0;
+        o.tex = b.type == NH_BSDF_DIFFUSE || b.type == NH_BSDF_DISNEY ? (int)b.albedo_texture : 0;
+    }
+    if (!dz.empty()) {
+        nhd::DDisney *recs = nullptr;
+        if (int rc_ = disney_upload(c, c->scene_bufs, dz, dz_albedo, &recs)) return rc_;
+        for (size_t k = 0; k < dz_owner.size(); ++k) disney_set_record(db[dz_owner[k]], recs + k);
     }
     std::vector<nhd::DTex> dt(d->n_textures);
     for (uint32_t i = 0; i < d->n_textures; ++i) {
@@ -695,12 +750,27 @@ int nh_upload_scene(nh_ctx *c, const nh_scene_desc *d) {
 
     c->shapes.assign(d->shapes, d->shapes + d->n_shapes);
     c->shape_bsdf_type.clear();
+    c->shape_bsdf_real.clear();
     unsigned types = 0;
     for (uint32_t i = 0; i < d->n_shapes; ++i) {
-        const int t = d->bsdfs[d->shapes[i].bsdf].type & 3;
-        c->shape_bsdf_type.push_back(t);
+        const int t = d->bsdfs[d->shapes[i].bsdf].type;  // 0..4 (checked above)
+        c->shape_bsdf_real.push_back(t);
         types |= 1u << t;
     }
+    // The material key of the sorted queues is two bits of the primitive record (nh_traverse.h kPrimMatShift), four
+    // classes, and only orders the shading work (which lane shades which path). The four older types keep their own
+    // value; Disney takes the key of a type the scene does not use -- microfacet's, else mirror's, else dielectric's,
+    // else diffuse's -- so it ranks as a class of its own in every scene but one that uses all five types, where it
+    // shares diffuse's (both sample the cosine lobe). Every reader of the key only ranks by it; the isolated-sphere
+    // marking reads the shape's real type (shape_bsdf_real).
+    int disney_key = 0;
+    for (int k : {NH_BSDF_MICROFACET, NH_BSDF_MIRROR, NH_BSDF_DIELECTRIC, NH_BSDF_DIFFUSE})
+        if (!(types & (1u << k))) {
+            disney_key = k;
+            break;
+        }
+    for (int t : c->shape_bsdf_real) c->shape_bsdf_type.push_back(t == NH_BSDF_DISNEY ? disney_key : t);
+    c->disney = (types & (1u << NH_BSDF_DISNEY)) != 0;
     c->n_bsdf_types = __builtin_popcount(types);
     c->specular = (types & ((1u << NH_BSDF_MIRROR) | (1u << NH_BSDF_DIELECTRIC))) != 0;
     // any BSDF with an albedo texture or shape with a normal map (wf_bounce_rr's lean instantiation has no lookup)
@@ -798,15 +868,16 @@ static void prims_near_box(const std::vector<float4> &nodes, const std::vector<i
 // Marks dielectric spheres whose box, grown by 2m (m = 1e-4 of the scene extent), is apart from every other
 // primitive's box (the isolated-sphere closest hit of nh_traverse.h `trace_next`); m goes into the record.
 static int mark_isolated_spheres(std::vector<float4> &prims, const std::vector<float4> &nodes,
-                                 const std::vector<int2> &leaves, int root_kind) {
+                                 const std::vector<int2> &leaves, int root_kind, const std::vector<int> &shape_bsdf) {
     const char *e = std::getenv("NH_ISO_SPHERE");
     if (e && e[0] == '0') return 0;
     const size_t n = prims.size() / 3;
     std::vector<size_t> sph;
     for (size_t k = 0; k < n; ++k) {
-        int bits;
+        int bits, shape;
         std::memcpy(&bits, &prims[3 * k + 2].w, 4);
-        if ((bits & nhd::kPrimSphere) && ((bits >> nhd::kPrimMatShift) & 3) == nhd::BSDF_DIELECTRIC) sph.push_back(k);
+        std::memcpy(&shape, &prims[3 * k + 1].w, 4);  // (the record's key bits may be a Disney BSDF's borrowed key)
+        if ((bits & nhd::kPrimSphere) && shape_bsdf[(size_t)shape] == nhd::BSDF_DIELECTRIC) sph.push_back(k);
     }
     if (sph.empty()) return 0;
     auto prim_box = [&](size_t k, double lo[3], double hi[3]) {
@@ -1184,7 +1255,7 @@ int nh_upload_bvh(nh_ctx *c, const nh_bvh_desc *b) {
             p[2] = make_float4(p2[0], p2[1], p2[2], f0);
         }
     }
-    S.iso_spheres = mark_isolated_spheres(prims, nodes, leaves, S.root_kind);
+    S.iso_spheres = mark_isolated_spheres(prims, nodes, leaves, S.root_kind, c->shape_bsdf_real);
     // leaf-end bits: the 4-wide traversal walks a leaf's records until this bit
     for (const int2 &lf : leaves)
         if (lf.y > 0) {
@@ -1649,7 +1720,7 @@ static int pool_handoff(nh_ctx *c, WfPool &p, WfPool &T, int bound, hipEvent_t *
     HIP_TRY(c, hipStreamWaitEvent(T.stream, p.ev_handoff, 0));
     HIP_TRY(c, hipEventRecord(ev[1], T.stream));
     HIP_TRY(c, hipEventRecord(ev[2], T.stream));
-    nh::launch_wf_tail_rr(c->d_scene, c->tv, L, T.job.ordered, T.job.stats, bound, c->specular,
+    NH_LAUNCH(c, launch_wf_tail_rr)(c->d_scene, c->tv, L, T.job.ordered, T.job.stats, bound, c->specular,
                           !c->specular && !c->textured, c->normal_mapped, T.trait, T.stream);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(ev[3], T.stream));
@@ -1715,9 +1786,9 @@ static int pool_enqueue(nh_ctx *c, WfPool &p) {
         HIP_TRY(c, hipEventRecord(ev[2], p.stream));
         if (it > 0 && (int64_t)bound <= p.tail_at) {
             if (p.rr)
-                nh::launch_wf_tail_rr(c->d_scene, c->tv, L, ordered, stats, bound, c->specular, !c->specular && !c->textured,
-                                      c->normal_mapped, p.trait, p.stream);
-            else nh::launch_wf_tail(c->d_scene, c->tv, L, ordered, stats, false, bound, c->depth, p.stream);
+                NH_LAUNCH(c, launch_wf_tail_rr)(c->d_scene, c->tv, L, ordered, stats, bound, c->specular,
+                                                !c->specular && !c->textured, c->normal_mapped, p.trait, p.stream);
+            else NH_LAUNCH(c, launch_wf_tail)(c->d_scene, c->tv, L, ordered, stats, false, bound, c->depth, p.stream);
             HIP_TRY(c, hipGetLastError());
             HIP_TRY(c, hipEventRecord(ev[3], p.stream));
             p.tail = true;
@@ -1725,9 +1796,10 @@ static int pool_enqueue(nh_ctx *c, WfPool &p) {
             p.state = WfPool::SPLAT;
             return NH_OK;
         }
-        if (p.rr) nh::launch_wf_bounce_rr(c->d_scene, c->tv, L, ordered, stats, p.sorted, !c->specular && !c->textured,
-                                          c->normal_mapped, p.trait, bound, p.stream);
-        else nh::launch_wf_bounce(c->d_scene, c->tv, L, ordered, stats, p.sorted, bound, p.stream);
+        if (p.rr) NH_LAUNCH(c, launch_wf_bounce_rr)(c->d_scene, c->tv, L, ordered, stats, p.sorted,
+                                                    !c->specular && !c->textured, c->normal_mapped, p.trait, bound,
+                                                    p.stream);
+        else NH_LAUNCH(c, launch_wf_bounce)(c->d_scene, c->tv, L, ordered, stats, p.sorted, bound, p.stream);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipEventRecord(ev[3], p.stream));
         if (int rc_ = count_service(c, p, slot[in ^ 1], slot[in], it)) return rc_;
@@ -1753,7 +1825,7 @@ static int pool_enqueue(nh_ctx *c, WfPool &p) {
         HIP_TRY(c, hipEventRecord(ev[2], p.stream));
     }
     if (it > 0 && (int64_t)bound <= p.tail_at) {
-        nh::launch_wf_tail(c->d_scene, c->tv, L, ordered, stats, p.wide ? c->wide_w : 0, bound, c->depth, p.stream);
+        NH_LAUNCH(c, launch_wf_tail)(c->d_scene, c->tv, L, ordered, stats, p.wide ? c->wide_w : 0, bound, c->depth, p.stream);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipEventRecord(ev[3], p.stream));
         p.tail = true;
@@ -1761,7 +1833,7 @@ static int pool_enqueue(nh_ctx *c, WfPool &p) {
         p.state = WfPool::SPLAT;
         return NH_OK;
     }
-    nh::launch_wf_shade(c->d_scene, c->tv, L, p.shade_sorted, c->normal_mapped, bound, p.stream);
+    NH_LAUNCH(c, launch_wf_shade)(c->d_scene, c->tv, L, p.shade_sorted, c->normal_mapped, bound, p.stream);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(ev[3], p.stream));
     if (int rc_ = count_service(c, p, slot[in ^ 1], slot[in], it)) return rc_;
@@ -2175,7 +2247,7 @@ int nh_render(nh_ctx *c, const nh_render_req *q) {
             HIP_TRY(c, hipEventCreate(&ev.b));
             HIP_TRY(c, hipEventCreate(&ev.d));
             HIP_TRY(c, hipEventRecord(ev.a, c->stream));
-            nh::launch_path(c->d_scene, c->tv, L, q->traversal != NH_TRAVERSAL_REFERENCE, q->collect_stats != 0,
+            NH_LAUNCH(c, launch_path)(c->d_scene, c->tv, L, q->traversal != NH_TRAVERSAL_REFERENCE, q->collect_stats != 0,
                             c->depth, c->integrator == NH_INTEGRATOR_PATH_MIS && !c->normal_mapped, c->stream);
             HIP_TRY(c, hipGetLastError());
             HIP_TRY(c, hipEventRecord(ev.b, c->stream));
@@ -2245,6 +2317,68 @@ int nh_render(nh_ctx *c, const nh_render_req *q) {
         c->stats.tail_shadow_boxes_tested += ta[2];
         c->stats.tail_shadow_prims_tested += ta[3];
     }
+    return NH_OK;
+}
+
+int nh_bsdf_query(nh_ctx *c, const nh_bsdf *b, const float *albedo, int32_t mode, int32_t n, const float *wi,
+                  const float *wo, const float *sample, float *wo_out, float *value, float *pdf, int32_t *measure) {
+    if (!c) return NH_ERR_INVALID;
+    if (!b || n < 0 || !wi || !value || !pdf) return fail(c, "nh_bsdf_query: null argument"), NH_ERR_INVALID;
+    if (b->type < NH_BSDF_DIFFUSE || b->type > NH_BSDF_DISNEY) return fail(c, "unknown BSDF type"), NH_ERR_INVALID;
+    if (mode != NH_BSDF_QUERY_EVAL && mode != NH_BSDF_QUERY_SAMPLE)
+        return fail(c, "nh_bsdf_query: unknown mode"), NH_ERR_INVALID;
+    if (mode == NH_BSDF_QUERY_EVAL ? !wo : (!sample || !wo_out || !measure))
+        return fail(c, "nh_bsdf_query: the mode's arrays are missing"), NH_ERR_INVALID;
+    if (n == 0) return NH_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    std::vector<void *> bufs;  // freed on every return
+    struct Free {
+        std::vector<void *> &v;
+        ~Free() { free_all(v); }
+    } guard{bufs};
+    nh_disney::nh::BsdfQuery q;
+    std::memset(&q, 0, sizeof(q));
+    DBsdf &o = q.bsdf;
+    o.type = b->type;
+    o.ar = b->albedo[0]; o.ag = b->albedo[1]; o.ab = b->albedo[2];
+    o.alpha = b->alpha; o.int_ior = b->int_ior; o.ext_ior = b->ext_ior; o.ks = b->ks;
+    o.kr = b->kd[0]; o.kg = b->kd[1]; o.kb = b->kd[2];
+    // no texture table here: tex only selects a Disney BSDF's per-query route (albedo stands in for the lookup)
+    o.tex = b->type == NH_BSDF_DISNEY && b->albedo_texture ? 1 : 0;
+    for (int k = 0; k < 3; ++k) q.albedo[k] = albedo ? albedo[k] : b->albedo[k];
+    if (b->type == NH_BSDF_DISNEY) {
+        nhd::DDisney *rec = nullptr;
+        const std::vector<nhd::DDisney> recs{disney_record(*b)};
+        const std::vector<float> alb(q.albedo, q.albedo + 3);
+        if (int rc = disney_upload(c, bufs, recs, alb, &rec)) return rc;
+        disney_set_record(o, rec);
+    }
+    q.mode = mode;
+    q.n = n;
+    const size_t sn = (size_t)n;
+    if (int rc = upload(c, bufs, wi, 3 * sn, &q.wi)) return rc;
+    if (mode == NH_BSDF_QUERY_EVAL) {
+        if (int rc = upload(c, bufs, wo, 3 * sn, &q.wo)) return rc;
+    } else {
+        if (int rc = upload(c, bufs, sample, 2 * sn, &q.sample)) return rc;
+    }
+    void *out = nullptr;  // wo_out (3n), value (3n), pdf (n), measure (n)
+    HIP_TRY(c, hipMalloc(&out, 8 * sn * sizeof(float)));
+    bufs.push_back(out);
+    float *f = static_cast<float *>(out);
+    q.wo_out = f;
+    q.value = f + 3 * sn;
+    q.pdf = f + 6 * sn;
+    q.measure = reinterpret_cast<int *>(f + 7 * sn);
+    nh_disney::nh::launch_bsdf_query(q, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<float> host(8 * sn);
+    HIP_TRY(c, hipMemcpyAsync(host.data(), out, host.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (wo_out) std::memcpy(wo_out, host.data(), 3 * sn * sizeof(float));
+    std::memcpy(value, host.data() + 3 * sn, 3 * sn * sizeof(float));
+    std::memcpy(pdf, host.data() + 6 * sn, sn * sizeof(float));
+    if (measure) std::memcpy(measure, host.data() + 7 * sn, sn * sizeof(float));
     return NH_OK;
 }
 

@@ -11,6 +11,7 @@
 #pragma clang fp contract(off)
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 namespace nhd {
@@ -165,7 +166,15 @@ NHD void sample_jitter_h(uint64_t h, uint64_t sample, float &jx, float &jy) {
 
 // ---- scene records -----------------------------------------------------------
 enum : int { SHAPE_MESH = 0, SHAPE_SPHERE = 1 };
-enum : int { BSDF_DIFFUSE = 0, BSDF_MIRROR = 1, BSDF_DIELECTRIC = 2, BSDF_MICROFACET = 3 };
+enum : int { BSDF_DIFFUSE = 0, BSDF_MIRROR = 1, BSDF_DIELECTRIC = 2, BSDF_MICROFACET = 3, BSDF_DISNEY = 4 };
+// The Disney branch of bsdf_eval / bsdf_pdf / bsdf_sample exists only in translation units built with -DNH_DISNEY
+// (the nh_disney:: copies of the render kernels, chosen at upload for scenes with a Disney BSDF, and nh_api.hip's
+// BSDF query kernel): the kernels every other scene launches are compiled without it, unchanged.
+#ifdef NH_DISNEY
+constexpr bool kDisney = true;
+#else
+constexpr bool kDisney = false;
+#endif
 enum : int { EMITTER_AREA = 0, EMITTER_POINT = 1, EMITTER_ENVMAP = 2 };
 enum : int { M_UNKNOWN = 0, M_SOLID_ANGLE = 1, M_DISCRETE = 2 };
 
@@ -183,9 +192,28 @@ struct alignas(16) DShape {
 struct alignas(16) DBsdf {
     int type;
     float ar, ag, ab;      // diffuse albedo
-    float alpha, int_ior, ext_ior, ks;
+    // disney: alpha / int_ior are unused, their words hold the device address of the BSDF's DDisney side record
+    union { float alpha; uint32_t disney_lo; };
+    union { float int_ior; uint32_t disney_hi; };
+    float ext_ior, ks;
     float kr, kg, kb;      // microfacet kd
-    int tex;               // diffuse: 1 + albedo texture index (DScene::texs), 0 = the constant albedo
+    int tex;               // diffuse / disney: 1 + albedo texture index (DScene::texs), 0 = the constant albedo
+};
+// Disney (disney.cpp): the side record of a BSDF_DISNEY DBsdf, which holds its device address in the words of
+// (alpha, int_ior) (disney_lo / disney_hi, disney_rec) -- DBsdf itself stays 48 bytes for the kernels that stage it to LDS. The ten clamped
+// parameters, the terms of eval that depend on them alone (ax, ay: disney.cpp:152-153; GTR1's a2 - 1 and
+// M_PI * log(a2) of the clearcoat lobe: :164, :311-313), and the terms that depend on the albedo (Cdlin, Cspec0,
+// Csheen: :132-137) for the constant albedo -- formed once at upload by the device functions below (nh_api.hip
+// disney_fold_kernel), the same float operations in the same order as a textured albedo runs per hit.
+static_assert(sizeof(DBsdf) == 48 && offsetof(DBsdf, disney_lo) == 16 && offsetof(DBsdf, disney_hi) == 20 &&
+                  offsetof(DBsdf, ext_ior) == 24, "DBsdf layout (staged to LDS as three float4)");
+struct alignas(16) DDisney {
+    float metallic, subsurface, specular, roughness;
+    float specular_tint, anisotropic, sheen, sheen_tint;
+    float clearcoat, clearcoat_gloss, ax, ay;
+    float cc_a2m1, cc_pilog, pad0, pad1;
+    float cdlin[3], cspec0[3], csheen[3];
+    float pad2[3];
 };
 // Texture<Color3f> albedo (nh_texture): consttexture.cpp / checkerboard.cpp / PNGTexture.cpp
 enum : int { TEX_CONSTANT = 0, TEX_CHECKERBOARD = 1, TEX_PNG = 2 };
@@ -360,9 +388,118 @@ NHD float smith_g1(const DBsdf &b, F3 v, F3 m) {  // microfacet.cpp:69-89
     float a2 = a * a;
     return (3.535f * a + 2.181f * a2) / (1.0f + 2.276f * a + 2.577f * a2);
 }
+// ---- Disney (src/bsdf/disney.cpp:111-205) ----------------------------------------------------
+// Overloads. disney.cpp calls pow / log / sqrt unqualified on float arguments. common.h:39 includes ImathPlatform.h,
+// which includes <math.h>; with g++ that is libstdc++'s wrapper, whose using-declarations put std::'s float overloads
+// into the global namespace, so every call resolves to the float overload (without <math.h> the only global
+// candidates would be glibc's double functions; a probe with both include sets shows the switch):
+//   pow(vec.r(), 2.2f)  std::pow(float, float) = powf   -> f_pow: fp64 pow rounded once, as the other f_* functions
+//   pow(x, 2.f)         std::pow(float, float) = powf   -> x * x (powf(x, 2) is the correctly rounded square)
+//   log(a2)             std::log(float) = logf          -> f_log
+//   sqrt(..)            std::sqrt(float) = sqrtf        -> f_sqrt (correctly rounded)
+//   std::max(0.001f, ..) float                          -> e_max
+// M_PI and INV_PI are Nori's float constants (common.h:61-62), mix<float>(1.0, ..) converts its 1.0 to float: the
+// whole of eval is fp32 arithmetic. (disney.cpp calls no cos.)
+NHD float f_pow(float x, float y) { return (float)pow((double)x, (double)y); }
+NHD const DDisney *disney_rec(const DBsdf &b) {
+    return reinterpret_cast<const DDisney *>(((uint64_t)b.disney_hi << 32) | (uint64_t)b.disney_lo);
+}
+NHD float nori_clamp01(float v) { return v < 0.f ? 0.f : (v > 1.f ? 1.f : v); }  // common.h clamp(v, 0, 1)
+NHD float schlick_fresnel(float a) {                                             // disney.cpp:289-294
+    const float m = nori_clamp01(1.f - a), m2 = m * m;
+    return m2 * m2 * m;
+}
+NHD float mixf(float a, float b, float t) { return a + (b - a) * t; }  // disney.cpp:283-287
+struct DisneyCol {
+    F3 cdlin, cspec0, csheen;
+};
+// disney.cpp:132-137: mon2lin, Cdlum, Ctint (1 for a black albedo), Cspec0, Csheen. Out of line (as tex_eval): three
+// fp64 pows that only a textured albedo and the upload-time fold run. Arguments and result by value, in registers (a
+// record passed by reference would have to live in scratch memory).
+__device__ __noinline__ DisneyCol disney_colors(float specular, float specular_tint, float metallic, float sheen_tint,
+                                                F3 alb) {
+    DisneyCol c;
+    c.cdlin = f3(f_pow(alb.x, 2.2f), f_pow(alb.y, 2.2f), f_pow(alb.z, 2.2f));
+    const float lum = 0.3f * c.cdlin.x + 0.6f * c.cdlin.y + 0.1f * c.cdlin.z;
+    const F3 tint = lum > 0.f ? divs(c.cdlin, lum) : f3(1.f, 1.f, 1.f);
+    const float s8 = specular * 0.08f;
+    const F3 m = f3(mixf(1.f, tint.x, specular_tint), mixf(1.f, tint.y, specular_tint),
+                    mixf(1.f, tint.z, specular_tint));
+    const F3 a = scl(s8, m);
+    c.cspec0 = f3(mixf(a.x, c.cdlin.x, metallic), mixf(a.y, c.cdlin.y, metallic), mixf(a.z, c.cdlin.z, metallic));
+    c.csheen = f3(mixf(1.f, tint.x, sheen_tint), mixf(1.f, tint.y, sheen_tint), mixf(1.f, tint.z, sheen_tint));
+    return c;
+}
+// the direction-independent scalars (disney.cpp:151-153, :164 with GTR1's :311-313), from the ten parameters
+NHD void disney_fold_params(DDisney &p) {
+    const float aspect = f_sqrt(1.f - p.anisotropic * 0.9f);
+    p.ax = e_max(0.001f, p.roughness * p.roughness / aspect);
+    p.ay = e_max(0.001f, p.roughness * p.roughness * aspect);
+    const float a = mixf(0.1f, 0.001f, p.clearcoat_gloss), a2 = a * a;  // a < 1: GTR1's a >= 1 return never fires
+    p.cc_a2m1 = a2 - 1.f;
+    p.cc_pilog = kPi * f_log(a2);
+}
+NHD float smith_ggx_aniso(float nv, float vx, float vy, float ax, float ay) {  // disney.cpp:295-298
+    return 1.f / (nv + f_sqrt(vx * ax * vx * ax + vy * ay * vy * ay + nv * nv));
+}
+NHD float smith_ggx(float nv, float alpha_g) {  // disney.cpp:300-305
+    const float a = alpha_g * alpha_g, b = nv * nv;
+    return 1.f / (nv + f_sqrt(a + b - a * b));
+}
+// Disney::eval (disney.cpp:111-174): L = wi, V = wo, X = (1, 0, 0), Y = (0, 1, 0) (so H.dot(X) = H.x + 0 etc.); no
+// measure check. alb is read only when the albedo is textured (b.tex): else the colours folded at upload.
+NHD F3 disney_eval(const DBsdf &b, F3 L, F3 V, F3 alb) {
+    const float ndl = L.z, ndv = V.z;
+    if (ndl < kEps || ndv < kEps) return f3(0, 0, 0);
+    const DDisney p = *disney_rec(b);
+    DisneyCol c;
+    if (b.tex) {
+        c = disney_colors(p.specular, p.specular_tint, p.metallic, p.sheen_tint, alb);
+    } else {
+        c.cdlin = f3(p.cdlin[0], p.cdlin[1], p.cdlin[2]);
+        c.cspec0 = f3(p.cspec0[0], p.cspec0[1], p.cspec0[2]);
+        c.csheen = f3(p.csheen[0], p.csheen[1], p.csheen[2]);
+    }
+    const F3 H = normalized(add(L, V));
+    const float ndh = H.z, ldh = dot(L, H);
+    // diffuse fresnel (:140-143)
+    const float FL = schlick_fresnel(ndl), FV = schlick_fresnel(ndv);
+    const float fd90 = 0.5f + 2.f * ldh * ldh * p.roughness;
+    const float Fd = mixf(1.f, fd90, FL) * mixf(1.f, fd90, FV);
+    // Hanrahan-Krueger subsurface approximation (:146-148)
+    const float fss90 = ldh * ldh * p.roughness;
+    const float Fss = mixf(1.f, fss90, FL) * mixf(1.f, fss90, FV);
+    const float ss = 1.25f * (Fss * (1.f / (ndl + ndv) - 0.5f) + 0.5f);
+    // specular (:151-158); GTR2_aniso (:315-318) with pow(x, 2.f) as x * x
+    const float hx = H.x / p.ax, hy = H.y / p.ay;
+    const float g = hx * hx + hy * hy + ndh * ndh;
+    const float Ds = 1.f / (kPi * p.ax * p.ay * (g * g));
+    const float FH = schlick_fresnel(ldh);
+    const F3 Fs = f3(mixf(c.cspec0.x, 1.f, FH), mixf(c.cspec0.y, 1.f, FH), mixf(c.cspec0.z, 1.f, FH));
+    float Gs = smith_ggx_aniso(ndl, L.x, L.y, p.ax, p.ay);
+    Gs *= smith_ggx_aniso(ndv, V.x, V.y, p.ax, p.ay);
+    // sheen (:161)
+    const F3 Fsheen = scl(FH * p.sheen, c.csheen);
+    // clearcoat (:164-166); GTR1 (:307-314) with its a2 - 1 and M_PI * log(a2) from the record
+    const float t1 = 1.f + p.cc_a2m1 * ndh * ndh;
+    const float Dr = p.cc_a2m1 / (p.cc_pilog * t1);
+    const float Fr = mixf(0.04f, 1.f, FH);
+    const float Gr = smith_ggx(ndl, 0.25f) * smith_ggx(ndv, 0.25f);
+    // :168
+    const float dm = kInvPi * mixf(Fd, ss, p.subsurface), om = 1.f - p.metallic;
+    const float cc = 0.25f * p.clearcoat * Gr * Fr * Dr;
+    F3 r = f3((dm * c.cdlin.x + Fsheen.x) * om + Gs * Fs.x * Ds + cc, (dm * c.cdlin.y + Fsheen.y) * om + Gs * Fs.y * Ds + cc,
+              (dm * c.cdlin.z + Fsheen.z) * om + Gs * Fs.z * Ds + cc);
+    // :171-172, Color3f::getLuminance (color.h)
+    const float lum = r.x * 0.212671f + r.y * 0.715160f + r.z * 0.072169f;
+    if (lum > 1.f) r = divs(r, lum);
+    return r;
+}
+
 // alb: the diffuse albedo at the query's uv (m_albedo->eval(bRec.uv): the constant albedo, or its texture's
 // value, nh_shade.h bsdf_albedo); unused by the other BSDFs
 NHD F3 bsdf_eval(const DBsdf &b, F3 wi, F3 wo, int measure, F3 alb) {
+    if (kDisney && b.type == BSDF_DISNEY) return disney_eval(b, wi, wo, alb);
     if (b.type == BSDF_DIFFUSE) {  // diffuse.cpp:94-103
         if (measure != M_SOLID_ANGLE || wi.z <= 0 || wo.z <= 0) return f3(0, 0, 0);
         return f3(alb.x * kInvPi, alb.y * kInvPi, alb.z * kInvPi);
@@ -379,7 +516,7 @@ NHD F3 bsdf_eval(const DBsdf &b, F3 wi, F3 wo, int measure, F3 alb) {
     return f3(0, 0, 0);
 }
 NHD float bsdf_pdf(const DBsdf &b, F3 wi, F3 wo, int measure) {
-    if (b.type == BSDF_DIFFUSE) {  // diffuse.cpp:106-120
+    if (b.type == BSDF_DIFFUSE || (kDisney && b.type == BSDF_DISNEY)) {  // diffuse.cpp:106-120, disney.cpp:198-205
         if (measure != M_SOLID_ANGLE || wi.z <= 0 || wo.z <= 0) return 0.0f;
         return kInvPi * wo.z;
     }
@@ -447,6 +584,14 @@ NHD F3 bsdf_sample(const DBsdf &b, F3 wi, float sx, float sy, F3 &wo, int &measu
             float p = bsdf_pdf(b, wi, wo, M_UNKNOWN);
             return f3(e.x / p * wo.z, e.y / p * wo.z, e.z / p * wo.z);
         }
+    }
+    if (kDisney && b.type == BSDF_DISNEY) {  // disney.cpp:176-196: returns eval itself, not eval * cos / pdf
+        if (wi.z <= 0) return f3(0, 0, 0);
+        measure = M_SOLID_ANGLE;
+        wo = cosine_hemisphere(sx, sy);
+        const F3 col = disney_eval(b, wi, wo, alb);
+        if (bsdf_pdf(b, wi, wo, measure) < kEps) return f3(0, 0, 0);
+        return col;
     }
     return f3(0, 0, 0);
 }

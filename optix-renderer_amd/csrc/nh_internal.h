@@ -241,3 +241,37 @@ void launch_small_image(const nhd::Traversal &tv, int n_prim_f4, int pairs_off, 
                         hipStream_t st);
 void launch_wf_counts(const unsigned *src, unsigned *host_dst, int n_copy, unsigned *zero, int n_zero, hipStream_t st);
 }  // namespace nh
+
+// The Disney variant (nh_device.h kDisney). nh_kernels.hip and nh_wavefront.hip are compiled a second time with
+// -DNH_DISNEY, which puts everything they define into namespace nh_disney: the same kernels with the Disney branch of
+// bsdf_eval / bsdf_pdf / bsdf_sample compiled in. nh_upload_scene chooses the set (nh_ctx::disney): a scene without a
+// Disney BSDF launches exactly the nh:: kernels it always did. Only the launchers whose kernels shade are declared.
+namespace nh_disney {
+namespace nh {
+void launch_path(const nhd::DScene *S, const nhd::Traversal &tv, const PathLaunch &L, bool ordered, bool stats,
+                 int depth, bool pm, hipStream_t st);
+void launch_wf_shade(const nhd::DScene *S, const nhd::Traversal &tv, const WfLaunch &L, bool sort, bool nmap, int bound,
+                     hipStream_t st);
+void launch_wf_bounce(const nhd::DScene *S, const nhd::Traversal &tv, const WfLaunch &L, bool ordered, bool stats,
+                      bool sort, int bound, hipStream_t st);
+void launch_wf_bounce_rr(const nhd::DScene *S, const nhd::Traversal &tv, const WfLaunch &L, bool ordered, bool stats, bool sort,
+                         bool lean, bool nmap, bool trait, int bound, hipStream_t st);
+void launch_wf_tail_rr(const nhd::DScene *S, const nhd::Traversal &tv, const WfLaunch &L, bool ordered, bool stats, int bound,
+                       bool specular, bool lean, bool nmap, bool trait, hipStream_t st);
+void launch_wf_tail(const nhd::DScene *S, const nhd::Traversal &tv, const WfLaunch &L, bool ordered, bool stats,
+                    int wide, int bound, int depth, hipStream_t st);
+// nh_disney.hip. The direction-independent scalars and the constant-albedo colour terms of n DDisney records
+// (albedo: 3 floats per record), by the device functions eval uses for a textured albedo
+void launch_disney_fold(nhd::DDisney *recs, const float *albedo, int n, hipStream_t st);
+// nh_bsdf_query's kernel: bsdf_eval + bsdf_pdf (mode 0) or bsdf_sample + bsdf_pdf (mode 1) of one DBsdf, n queries
+struct BsdfQuery {
+    nhd::DBsdf bsdf;
+    float albedo[3];
+    int mode, n;
+    const float *wi, *wo, *sample;
+    float *wo_out, *value, *pdf;
+    int *measure;
+};
+void launch_bsdf_query(const BsdfQuery &q, hipStream_t st);
+}  // namespace nh
+}  // namespace nh_disney

@@ -19,6 +19,12 @@
 
 using namespace nhd;
 
+// Built a second time with -DNH_DISNEY (Makefile): the same kernels and launchers with the Disney branch of the BSDF
+// functions compiled in (nh_device.h kDisney), as nh_disney::nh::launch_* (nh_internal.h)
+#ifdef NH_DISNEY
+namespace nh_disney {
+#endif
+
 namespace {
 
 // PathMISIntegrator::Li (src/integrators/path_mis.cpp:16-150). Lanes of a wave stay in
@@ -471,6 +477,7 @@ __global__ __launch_bounds__(BLOCK, MINW) void nh_path_kernel(const DScene *__re
 // ---------------------------------------------------------------------------
 namespace nh {
 
+#ifndef NH_DISNEY  // the traversal entry points have no Disney copy
 template <int BLOCK, int DEPTH>
 static void launch_trace_d(const DScene *S, const Traversal &tv, const RayBatch &rb, const HitBatch &hb, int n,
                            bool any, bool ordered, bool stats, unsigned long long *ctr, hipStream_t st) {
@@ -516,6 +523,7 @@ void launch_trace_wide(const DScene *S, const Traversal &tv, const RayBatch &rb,
     }
 #undef NH_TW
 }
+#endif
 
 template <int BLOCK, int DEPTH, int MINW>
 static void launch_path_w(const DScene *S, const Traversal &tv, const PathLaunch &L, bool ordered, bool stats,
@@ -564,3 +572,7 @@ void launch_path(const DScene *S, const Traversal &tv, const PathLaunch &L, bool
 }
 
 }  // namespace nh
+
+#ifdef NH_DISNEY
+}  // namespace nh_disney
+#endif

@@ -34,6 +34,12 @@
 
 using namespace nhd;
 
+// Built a second time with -DNH_DISNEY (Makefile): the same kernels and launchers with the Disney branch of the BSDF
+// functions compiled in (nh_device.h kDisney), as nh_disney::nh::launch_* (nh_internal.h)
+#ifdef NH_DISNEY
+namespace nh_disney {
+#endif
+
 namespace {
 
 // Path flags. Stored (6 bits, packed with the path id into ray_d.w):
@@ -917,9 +923,17 @@ __device__ __forceinline__ bool shade_path(const DScene &S, const Traversal &tv,
 #ifndef NH_SHADE_WAVES
 #define NH_SHADE_WAVES 4
 #endif
+// The register budget of an nh_disney copy (waves per SIMD): 3 where cond holds -- the copies that spill at 4 with
+// Disney's eval inlined (wf_bounce_rr 64-112 B per lane, the sorting wf_shade and the counting wf_bounce 16-32 B) and
+// are spill-free at 3 (profiles/disney_kernel_resources.txt). Every other build: w, unchanged.
+#ifdef NH_DISNEY
+#define NH_DZ_WAVES(cond, w) ((cond) ? 3 : (w))
+#else
+#define NH_DZ_WAVES(cond, w) (w)
+#endif
 // NMAP: hit_info's normal maps (false for scenes without them, as the full RR-ahead bodies)
 template <bool SORT, bool NMAP = true>
-__global__ __launch_bounds__(256, NH_SHADE_WAVES) void wf_shade(const DScene *__restrict__ Sp, Traversal tv, WfLaunch L) {
+__global__ __launch_bounds__(256, NH_DZ_WAVES(SORT, NH_SHADE_WAVES)) void wf_shade(const DScene *__restrict__ Sp, Traversal tv, WfLaunch L) {
     __shared__ unsigned s_n[2], s_base[2];
     __shared__ unsigned s_cls[SORT ? 6 : 1];
     __shared__ short s_perm[SORT ? 256 : 1];
@@ -1005,7 +1019,7 @@ constexpr int kMatClasses = 5;  // 4 BSDF types + rays that leave the scene
 #define NH_BOUNCE_WAVES 4
 #endif
 template <bool ORDERED, bool STATS, bool SORT>
-__global__ __launch_bounds__(256, NH_BOUNCE_WAVES) void wf_bounce(const DScene *__restrict__ Sp, Traversal tv_g,
+__global__ __launch_bounds__(256, NH_DZ_WAVES(STATS, NH_BOUNCE_WAVES)) void wf_bounce(const DScene *__restrict__ Sp, Traversal tv_g,
                                                                   WfLaunch L) {
     __shared__ uint32_t stk[16 * 256];
     __shared__ unsigned s_n[kMatClasses], s_off[kMatClasses], s_base;
@@ -1333,7 +1347,7 @@ __device__ __forceinline__ bool bounce_path(const DScene &S, const ST &T, const 
 // TRAIT, BOUNCE: the diffuse area-light instantiations (launch_wf_bounce_trait), one for bounce 0 and one for the later
 // bounces; the later-bounce kernel issues its path's state loads before the staging barrier and uses them after it
 template <bool ORDERED, bool STATS, bool SORT, bool FULL = true, bool NMAP = FULL, bool TRAIT = false, int BOUNCE = -1>
-__global__ __launch_bounds__(NH_BOUNCE_TB, NH_BOUNCE_WAVES) void wf_bounce_rr(const DScene *__restrict__ Sp, Traversal tv_g,
+__global__ __launch_bounds__(NH_BOUNCE_TB, NH_DZ_WAVES(true, NH_BOUNCE_WAVES)) void wf_bounce_rr(const DScene *__restrict__ Sp, Traversal tv_g,
                                                                      WfLaunch L) {
     __shared__ uint32_t stk[16 * NH_BOUNCE_TB];
     __shared__ unsigned s_n[kMatClasses], s_off[kMatClasses], s_base;
@@ -1508,7 +1522,7 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(W))) void wf
 // Asynchronous tail hand-off: the chunk's live paths (RR-ahead state, 88 B each) are copied into a small buffer
 // of their own, densely from slot 0 (all in count shard 0; the other shards and groups are zeroed by the host),
 // so the pool's path state is free for the next chunk while this chunk's tail kernel runs on another stream.
-#if !defined(NH_WF_PART) || NH_WF_PART == 1  // non-template kernels: defined in one part only
+#if (!defined(NH_WF_PART) || NH_WF_PART == 1) && !defined(NH_DISNEY)  // non-template kernels: defined in one part only
 // After a bounce's appending kernel: its output counts (n_copy words) to the pool's pinned host ring, and the
 // count slot its input came from (dead now, the next bounce's output) zeroed -- one kernel in place of the
 // runtime's two blit kernels (a device-to-host copy and a memset) per bounce. The host reads the ring once the
@@ -1521,7 +1535,7 @@ __global__ __launch_bounds__(256) void wf_counts_kernel(const unsigned *src, uns
     __threadfence_system();
 }
 #endif
-#if !defined(NH_WF_PART) || NH_WF_PART == 1  // a non-template kernel: defined in one part only
+#if (!defined(NH_WF_PART) || NH_WF_PART == 1) && !defined(NH_DISNEY)  // non-template kernels: defined in one part only
 // bounce 0's camera rays of a thin-lens scene, for the persistent traversal kernels, whose refill code builds pinhole
 // rays only (camera_ray<false>: the lens arithmetic spilled it): the same camera_sample as every other kernel, stored
 // raw -- (origin, mint), (direction, maxt) -- in the input buffer's ray words, which bounce 0 does not use otherwise
@@ -1613,6 +1627,13 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(NH_TAIL_WAV
 
 // The launchers are split into parts so the build can compile this file as several translation units in parallel
 // (Makefile: -DNH_WF_PART=k; each part instantiates only its own kernels). Without NH_WF_PART: every part.
+// The nh_disney variant (-DNH_DISNEY) is built from parts 1 and 2 only, and of those only the launchers whose kernels
+// shade (NH_WF_SHADING_ONLY): traversal, queue and camera-ray kernels have no Disney copy.
+#ifdef NH_DISNEY
+#define NH_WF_SHADING_ONLY 1
+#else
+#define NH_WF_SHADING_ONLY 0
+#endif
 #ifdef NH_WF_PART
 #define NH_WF_HAS_PART(k) (NH_WF_PART == (k))
 #else
@@ -1621,7 +1642,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(NH_TAIL_WAV
 
 namespace nh {
 
-#if NH_WF_HAS_PART(0)
+#if NH_WF_HAS_PART(0) && !NH_WF_SHADING_ONLY
 int tree_top_nodes() { return kTopNodes; }
 #endif
 
@@ -1641,7 +1662,7 @@ static void launch_persistent(int want, hipStream_t st, const DScene *S, const T
     hipLaunchKernelGGL(KERN, dim3(std::min(want, resident)), dim3(128), 0, st, S, tv, L);
 }
 
-#if NH_WF_HAS_PART(0) || NH_WF_HAS_PART(3)
+#if (NH_WF_HAS_PART(0) || NH_WF_HAS_PART(3)) && !NH_WF_SHADING_ONLY
 template <int DEPTH>
 static void launch_wf_trace_d(const DScene *S, const Traversal &tv, const WfLaunch &L, bool ordered, bool stats,
                               bool shadow, bool persistent, int wide, int bound, hipStream_t st) {
@@ -1686,7 +1707,7 @@ static void launch_wf_trace_d(const DScene *S, const Traversal &tv, const WfLaun
 
 void launch_wf_trace_deep(const DScene *S, const Traversal &tv, const WfLaunch &L, bool ordered, bool stats,
                           bool shadow, bool persistent, int wide, int bound, int depth, hipStream_t st);
-#if NH_WF_HAS_PART(0)
+#if NH_WF_HAS_PART(0) && !NH_WF_SHADING_ONLY
 void launch_wf_trace(const DScene *S, const Traversal &tv, const WfLaunch &L, bool ordered, bool stats, bool shadow,
                      bool persistent, int wide, int bound, int depth, hipStream_t st) {
     if (depth <= 16) launch_wf_trace_d<16>(S, tv, L, ordered, stats, shadow, persistent, wide, bound, st);
@@ -1694,7 +1715,7 @@ void launch_wf_trace(const DScene *S, const Traversal &tv, const WfLaunch &L, bo
     else launch_wf_trace_deep(S, tv, L, ordered, stats, shadow, persistent, wide, bound, depth, st);
 }
 #endif
-#if NH_WF_HAS_PART(3)
+#if NH_WF_HAS_PART(3) && !NH_WF_SHADING_ONLY
 void launch_wf_trace_deep(const DScene *S, const Traversal &tv, const WfLaunch &L, bool ordered, bool stats,
                           bool shadow, bool persistent, int wide, int bound, int depth, hipStream_t st) {
     if (depth <= 64) launch_wf_trace_d<64>(S, tv, L, ordered, stats, shadow, persistent, wide, bound, st);
@@ -1722,6 +1743,7 @@ static void launch_wf_tail_d(const DScene *S, const Traversal &tv, const WfLaunc
 #undef NH_TL
 }
 
+#if !NH_WF_SHADING_ONLY
 void launch_wf_trace2(const DScene *S, const Traversal &tv, const WfLaunch &L, bool ordered, bool stats, int wide,
                       int bound, hipStream_t st) {
     // the wide trees are walked near-first only (nh_api.hip uses them for ordered traversals)
@@ -1735,6 +1757,7 @@ void launch_wf_trace2(const DScene *S, const Traversal &tv, const WfLaunch &L, b
     if (stats) launch_persistent<wf_trace_pt2<true, true>>(want, st, S, tv, L);
     else launch_persistent<wf_trace_pt2<true, false>>(want, st, S, tv, L);
 }
+#endif
 
 void launch_wf_tail(const DScene *S, const Traversal &tv, const WfLaunch &L, bool ordered, bool stats, int wide,
                     int bound, int depth, hipStream_t st) {
@@ -1766,7 +1789,9 @@ void launch_wf_bounce(const DScene *S, const Traversal &tv, const WfLaunch &L, b
 #if NH_WF_HAS_PART(2)
 void launch_wf_bounce_rr(const DScene *S, const Traversal &tv, const WfLaunch &L, bool ordered, bool stats, bool sort,
                          bool lean, bool nmap, bool trait, int bound, hipStream_t st) {
+#ifndef NH_DISNEY  // (a scene with a Disney BSDF never has the trait: part 4 is not built for the variant)
     if (trait && ordered && lean && !sort) return launch_wf_bounce_trait(S, tv, L, stats, bound, st);
+#endif
     int blocks = std::max(1, (bound + NH_BOUNCE_TB - 1) / NH_BOUNCE_TB);
     blocks = (blocks + kQueueShards - 1) / kQueueShards * kQueueShards;
     const size_t lds = 16 * (size_t)rr_lds_f4(L);
@@ -1800,13 +1825,23 @@ void launch_wf_tail_rr(const DScene *S, const Traversal &tv, const WfLaunch &L, 
     // 4-wave budget spilled 448 B per lane inside the bounce loop), the tail 4-6 % shorter, the C2 step level with 4
     // waves (profiles/round6_ab_tail_waves.txt). lean (NH_TAIL_LEAN=0 off): the FULL = false body
     const char *w = std::getenv("NH_TAIL_RR_WAVES");
-    const int waves = w ? (std::atoi(w) == 1 ? 1 : std::atoi(w) == 2 ? 2 : 4) : specular ? 1 : 2;
+    int waves = w ? (std::atoi(w) == 1 ? 1 : std::atoi(w) == 2 ? 2 : 4) : specular ? 1 : 2;
+#ifdef NH_DISNEY  // the 4-wave copies spill in every build and more with Disney's eval: the variant has none
+    if (waves == 4) waves = 2;
+#define NH_TR4(O, T)
+#else
+#define NH_TR4(O, T)                                                                                        \
+        else if (lean) hipLaunchKernelGGL((wf_tail_rr<O, T, 64, 4, false>), grid, dim3(64), lds, st, S, tv, L, coop); \
+        else hipLaunchKernelGGL((wf_tail_rr<O, T, 64, 4>), grid, dim3(64), lds, st, S, tv, L, coop);
+#endif
     const char *ln = std::getenv("NH_TAIL_LEAN");
     if (ln && ln[0] == '0') lean = false;
     const char *cp = std::getenv("NH_TAIL_COOP");  // lanes per path once <= 4 remain in a wave: 16 (default) or 1
     const int coop = cp && std::atoi(cp) == 1 ? 1 : 16;
     // the trait tail exists at the default shape only: 64 threads, 2 waves/SIMD, lean body
+#ifndef NH_DISNEY
     if (trait && ordered && lean && tb == 64 && waves == 2) return launch_wf_tail_trait(S, tv, L, stats, bound, coop, st);
+#endif
     // one path per lane: the grid covers the bound (tail bounds are <= kTailCap paths)
     const dim3 grid(std::max(1, (bound + tb - 1) / tb));
     const size_t lds = 16 * (size_t)rr_lds_f4(L);
@@ -1819,12 +1854,12 @@ void launch_wf_tail_rr(const DScene *S, const Traversal &tv, const WfLaunch &L, 
         else if (lean && waves == 2)                                                                        \
             hipLaunchKernelGGL((wf_tail_rr<O, T, 64, 2, false>), grid, dim3(64), lds, st, S, tv, L, coop);  \
         else if (waves == 2) hipLaunchKernelGGL((wf_tail_rr<O, T, 64, 2>), grid, dim3(64), lds, st, S, tv, L, coop); \
-        else if (lean) hipLaunchKernelGGL((wf_tail_rr<O, T, 64, 4, false>), grid, dim3(64), lds, st, S, tv, L, coop); \
-        else hipLaunchKernelGGL((wf_tail_rr<O, T, 64, 4>), grid, dim3(64), lds, st, S, tv, L, coop);           \
+        NH_TR4(O, T)                                                                                        \
     } while (0)
     if (ordered) { if (stats) NH_TR(true, true); else NH_TR(true, false); }
     else { if (stats) NH_TR(false, true); else NH_TR(false, false); }
 #undef NH_TR
+#undef NH_TR4
 }
 
 #endif
@@ -1855,7 +1890,7 @@ void launch_wf_tail_trait(const DScene *S, const Traversal &tv, const WfLaunch &
 }
 #endif
 
-#if NH_WF_HAS_PART(1)
+#if NH_WF_HAS_PART(1) && !NH_WF_SHADING_ONLY
 void launch_wf_camera_rays(const DScene *S, const WfLaunch &L, int bound, hipStream_t st) {
     const int blocks = std::min(std::max(1, (bound + 255) / 256), kTraceBlocksMax);
     hipLaunchKernelGGL(wf_camera_rays, dim3(blocks), dim3(256), 0, st, S, L);
@@ -1863,6 +1898,7 @@ void launch_wf_camera_rays(const DScene *S, const WfLaunch &L, int bound, hipStr
 #endif
 
 #if NH_WF_HAS_PART(1)
+#if !NH_WF_SHADING_ONLY
 void launch_wf_counts(const unsigned *src, unsigned *host_dst, int n_copy, unsigned *zero, int n_zero, hipStream_t st) {
     hipLaunchKernelGGL(wf_counts_kernel, dim3(1), dim3(256), 0, st, src, host_dst, n_copy, zero, n_zero);
 }
@@ -1875,6 +1911,7 @@ void launch_small_image(const Traversal &tv, int n_prim_f4, int pairs_off, int f
 void launch_wf_pack_rr(const WfLaunch &L, const WfBuf &dst, unsigned *dst_counts, int bound, hipStream_t st) {
     hipLaunchKernelGGL(wf_pack_rr, dim3(std::max(1, (bound + 255) / 256)), dim3(256), 0, st, L, dst, dst_counts);
 }
+#endif
 
 void launch_wf_shade(const DScene *S, const Traversal &tv, const WfLaunch &L, bool sort, bool nmap, int bound,
                      hipStream_t st) {
@@ -1890,3 +1927,7 @@ void launch_wf_shade(const DScene *S, const Traversal &tv, const WfLaunch &L, bo
 #endif
 
 }  // namespace nh
+
+#ifdef NH_DISNEY
+}  // namespace nh_disney
+#endif

@@ -683,6 +683,39 @@ nh_bsdf make_bsdf(const Obj &o, const std::string &base_dir, SceneData &sd) {
         float m12 = kd.y < kd.z ? kd.z : kd.y;
         float mx = kd.x < m12 ? m12 : kd.x;
         b.ks = 1 - mx;
+    } else if (o.type == "disney") {
+        // Disney (disney.cpp:22-42, :44-52, :88-109): the albedo as Diffuse's -- an "albedo" colour, else a
+        // <texture name="albedo"> child, else cloneAndInit's constant 0.5 -- and ten floats, each clamp(.., 0, 1)
+        // (common.h clamp). Any other property is never read: the reference's own scenes set "baseColor", which
+        // therefore changes nothing (those spheres render with albedo 0.5).
+        b.type = NH_BSDF_DISNEY;
+        const bool has_color = p.has("albedo");
+        V3 a = p.get_color("albedo", v3(0.5f, 0.5f, 0.5f));
+        b.albedo[0] = a.x; b.albedo[1] = a.y; b.albedo[2] = a.z;
+        auto unit = [&](const char *name, float def) {
+            const float v = p.get_float(name, def);
+            return v < 0.f ? 0.f : (v > 1.f ? 1.f : v);
+        };
+        b.metallic = unit("metallic", 0.f);
+        b.subsurface = unit("subsurface", 0.f);
+        b.specular = unit("specular", 0.5f);
+        b.roughness = unit("roughness", 0.5f);
+        b.specular_tint = unit("specularTint", 0.f);
+        b.anisotropic = unit("anisotropic", 0.f);
+        b.sheen = unit("sheen", 0.f);
+        b.sheen_tint = unit("sheenTint", 0.5f);
+        b.clearcoat = unit("clearcoat", 0.f);
+        b.clearcoat_gloss = unit("clearcoatGloss", 1.f);
+        bool have = has_color;
+        for (auto &ch : o.children) {
+            if (ch->tag != "texture") throw SceneError("Disney::addChild(<" + ch->tag + ">) is not supported!");
+            if (ch->props.get_string("name", "") != "albedo")
+                throw SceneError("The name of this texture does not match any field!");
+            if (have) throw SceneError("There is already an albedo defined!");
+            have = true;
+            sd.textures.push_back(make_texture(*ch, base_dir, sd));
+            b.albedo_texture = (uint32_t)sd.textures.size();
+        }
     } else {
         throw SceneError("BSDF type \"" + o.type + "\" is not supported by the HIP path");
     }

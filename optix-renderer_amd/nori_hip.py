@@ -30,6 +30,8 @@ _lib = C.CDLL(LIB_PATH)
 NH_OK = 0
 SHAPE_MESH, SHAPE_SPHERE = 0, 1
 BSDF_DIFFUSE, BSDF_MIRROR, BSDF_DIELECTRIC, BSDF_MICROFACET = 0, 1, 2, 3
+BSDF_DISNEY = 4  # disney.cpp
+BSDF_QUERY_EVAL, BSDF_QUERY_SAMPLE = 0, 1
 EMITTER_AREA, EMITTER_POINT, EMITTER_ENVMAP = 0, 1, 2
 INTEGRATOR_PATH_MIS, INTEGRATOR_PATH_MATS, INTEGRATOR_DIRECT_EMS, INTEGRATOR_DIRECT_MATS, INTEGRATOR_DIRECT_MIS = 0, 1, 2, 3, 4
 INTEGRATOR_DIRECT = 5  # the point-light `direct` integrator of scenes/pa1 (direct.cpp)
@@ -54,9 +56,15 @@ class nh_shape(C.Structure):
                 ("pdf_offset", _u32), ("pdf_normalization", _f), ("normal_map", _u32)]
 
 
+# nh_bsdf's Disney parameters in the struct's order, with the defaults of disney.cpp:32-41
+DISNEY_PARAMS = ("metallic", "subsurface", "specular", "roughness", "specular_tint", "anisotropic", "sheen",
+                 "sheen_tint", "clearcoat", "clearcoat_gloss")
+DISNEY_DEFAULTS = dict(zip(DISNEY_PARAMS, (0.0, 0.0, 0.5, 0.5, 0.0, 0.0, 0.0, 0.5, 0.0, 1.0)))
+
+
 class nh_bsdf(C.Structure):
     _fields_ = [("type", _i32), ("albedo", _f * 3), ("alpha", _f), ("int_ior", _f), ("ext_ior", _f),
-                ("kd", _f * 3), ("ks", _f), ("albedo_texture", _u32)]
+                ("kd", _f * 3), ("ks", _f), ("albedo_texture", _u32)] + [(n, _f) for n in DISNEY_PARAMS]
 
 
 TEXTURE_CONSTANT, TEXTURE_CHECKERBOARD, TEXTURE_PNG = 0, 1, 2
@@ -218,6 +226,7 @@ _sig("nh_reset_stats", _i32, _vp)
 _sig("nh_reduce_framebuffers", _i32, C.POINTER(_vp), _i32, _i32)
 _sig("nh_denoise", _i32, _vp, C.POINTER(nh_denoiser))
 _sig("nh_denoise_image", _i32, _vp, _fp, _i32, _i32, _i32, C.POINTER(nh_denoiser))
+_sig("nh_bsdf_query", _i32, _vp, C.POINTER(nh_bsdf), _fp, _i32, _i32, _fp, _fp, _fp, _fp, _fp, _fp, C.POINTER(_i32))
 _sig("nh_last_error", C.c_char_p, _vp)
 
 lib = _lib
@@ -292,6 +301,8 @@ class Scene:
         m = kdf[0] if not (kdf[0] < m) else m
         b.ks = float(np.float32(1) - np.float32(m))
         b.albedo_texture = kw.get("albedo_texture", 0)
+        for n in DISNEY_PARAMS:  # as Disney's constructor: its default, clamped to [0, 1]
+            setattr(b, n, min(max(float(kw.get(n, DISNEY_DEFAULTS[n])), 0.0), 1.0))
         _host_check(_lib.nh_scene_set_bsdf(self._h, shape, C.byref(b)), "set_bsdf")
 
     def add_texture(self, type: int, value1=(0, 0, 0), value2=(1, 1, 1), delta=(0, 0), scale=(1, 1), texels=None,
@@ -487,6 +498,32 @@ class Context:
         out = np.array(rgbw, dtype=np.float32, order="C", copy=True)
         h, w = out.shape[0] - 2 * border, out.shape[1] - 2 * border
         self._check(_lib.nh_denoise_image(self._h, _fptr(out), w, h, border, C.byref(params)), "denoise_image")
+        return out
+
+    def bsdf_query(self, bsdf: nh_bsdf, wi: np.ndarray, wo: np.ndarray = None, sample: np.ndarray = None,
+                   albedo=None) -> dict:
+        """nh_bsdf_query: n BSDF queries by the render kernels' own device functions. wi: (n, 3) local directions.
+        With wo (n, 3): {"value": eval (n, 3), "pdf": (n,)}, solid-angle measure. With sample (n, 2) instead:
+        {"wo": (n, 3), "value": the sample's weight (n, 3), "pdf": pdf(wi, wo) (n,), "measure": (n,)}. albedo: the
+        colour standing in for the albedo texture's value (default: bsdf.albedo)."""
+        if (wo is None) == (sample is None):
+            raise ValueError("bsdf_query: give either wo (eval) or sample (sample)")
+        wi = np.ascontiguousarray(wi, dtype=np.float32).reshape(-1, 3)
+        n = len(wi)
+        out = {"value": np.zeros((n, 3), np.float32), "pdf": np.zeros(n, np.float32)}
+        alb = None if albedo is None else np.ascontiguousarray(albedo, dtype=np.float32).reshape(3)
+        if wo is not None:
+            wo = np.ascontiguousarray(wo, dtype=np.float32).reshape(n, 3)
+            rc = _lib.nh_bsdf_query(self._h, C.byref(bsdf), None if alb is None else _fptr(alb), BSDF_QUERY_EVAL, n,
+                                    _fptr(wi), _fptr(wo), None, None, _fptr(out["value"]), _fptr(out["pdf"]), None)
+        else:
+            sample = np.ascontiguousarray(sample, dtype=np.float32).reshape(n, 2)
+            out["wo"] = np.zeros((n, 3), np.float32)
+            out["measure"] = np.zeros(n, np.int32)
+            rc = _lib.nh_bsdf_query(self._h, C.byref(bsdf), None if alb is None else _fptr(alb), BSDF_QUERY_SAMPLE, n,
+                                    _fptr(wi), None, _fptr(sample), _fptr(out["wo"]), _fptr(out["value"]),
+                                    _fptr(out["pdf"]), out["measure"].ctypes.data_as(C.POINTER(_i32)))
+        self._check(rc, "bsdf_query")
         return out
 
     def trace(self, o: np.ndarray, d: np.ndarray, mint: np.ndarray, maxt: np.ndarray, any_hit=False,
