@@ -30,11 +30,12 @@ WF_PARTS := 0 1 2 3 4
 HIP_OBJ  := $(patsubst $(PKG)/csrc/%.hip,$(OBJDIR)/hip_%.o,$(HIP_SRC)) \
             $(foreach k,$(WF_PARTS),$(OBJDIR)/hip_nh_wavefront_p$(k).o)
 # The Disney variant (nh_device.h kDisney): the megakernel file and the shading parts of nh_wavefront.hip compiled once
-# more with -DNH_DISNEY, as namespace nh_disney, plus the Disney-only kernels of nh_disney.hip. Scenes without a Disney
-# BSDF never launch these (nh_api.hip NH_LAUNCH). Only what shades is built: parts 0 and 3 (traversal kernels) and
+# more with -DNH_DISNEY, as namespace nh_disney, plus the Disney-only kernels of nh_disney.hip and the emitter query
+# kernel. It also holds the spot / directional light branches (kExtLights). Scenes without a Disney BSDF or one of
+# those lights never launch these (nh_api.hip NH_LAUNCH). Only what shades is built: parts 0 and 3 (traversal kernels) and
 # part 4 (the diffuse area-light instantiations) have no variant, and parts 1 and 2 leave their other kernels out.
 DZ_PARTS := 1 2
-HIP_OBJ  += $(OBJDIR)/hipdz_nh_kernels.o $(OBJDIR)/hipdz_nh_disney.o \
+HIP_OBJ  += $(OBJDIR)/hipdz_nh_kernels.o $(OBJDIR)/hipdz_nh_disney.o $(OBJDIR)/hipdz_nh_emitter_query.o \
             $(foreach k,$(DZ_PARTS),$(OBJDIR)/hipdz_nh_wavefront_p$(k).o)
 HIP_DEPS := $(wildcard $(PKG)/csrc/*.h) include/nori_hip.h
 # The wavefront kernels build without LLVM's machine-level LICM: it hoists loop invariants out of the traversal, bounce

@@ -54,7 +54,8 @@ extern "C" {
 
 enum { NH_SHAPE_MESH = 0, NH_SHAPE_SPHERE = 1 };
 enum { NH_BSDF_DIFFUSE = 0, NH_BSDF_MIRROR = 1, NH_BSDF_DIELECTRIC = 2, NH_BSDF_MICROFACET = 3, NH_BSDF_DISNEY = 4 };
-enum { NH_EMITTER_AREA = 0, NH_EMITTER_POINT = 1, NH_EMITTER_ENVMAP = 2 };
+enum { NH_EMITTER_AREA = 0, NH_EMITTER_POINT = 1, NH_EMITTER_ENVMAP = 2, NH_EMITTER_SPOT = 3,
+       NH_EMITTER_DIRECTIONAL = 4 };
 /* path_mis (src/integrators/path_mis.cpp), path_mats (path_mats.cpp), the single-bounce
  * direct_ems / direct_mats / direct_mis (direct_ems.cpp, direct_mats.cpp, direct_mis.cpp), the
  * point-light `direct` integrator (direct.cpp, scenes/pa1) and the `normals` integrator of the normal-map scenes
@@ -134,15 +135,31 @@ typedef struct nh_texture {
     int32_t pad;
 } nh_texture;
 
-/* One Nori Emitter (src/emitters/{arealight,pointlight}.cpp). */
+/* One Nori Emitter (src/emitters/{arealight,pointlight,environmentmap,spotlight,directionalLight}.cpp).
+ * nh_upload_scene rejects a type outside NH_EMITTER_AREA..NH_EMITTER_DIRECTIONAL with NH_ERR_INVALID. */
 typedef struct nh_emitter {
     int32_t type;            /* NH_EMITTER_* */
-    int32_t shape;           /* area light: owning shape */
-    float radiance[3];       /* area: radiance; point: power */
+    int32_t shape;           /* area light: owning shape, else -1 */
+    float radiance[3];       /* area / directional: radiance; point: power / (4 pi); spot: the intensity
+                                I = power / 2 / pi / (1 - 0.5 (cos_total_width + cos_falloff_start))
+                                (spotlight.cpp:50, :67-69) */
     float light_prob;        /* lightWeight (emitter DiscretePDF weight) */
-    float position[3];       /* point light */
+    float position[3];       /* point / spot light */
     float pad;
 } nh_emitter;
+
+/* What a spot / directional light holds beyond its nh_emitter, which keeps its 32 bytes: entry i of
+ * nh_scene_desc.emitter_ext belongs to emitter i; the entries of other emitter types are not read. */
+typedef struct nh_emitter_ext {
+    float direction[3];      /* m_direction: the `direction` property, normalized (non-zero and finite) */
+    float cos_total_width;   /* spot: cos(degToRad(totalwidth / 2)) (spotlight.cpp:68) */
+    float frame_s[3];        /* m_coord = Frame(direction) (spot: Frame(direction.normalized()), spotlight.cpp:21) */
+    float cos_falloff_start; /* spot: cos(degToRad(falloffstart)) (spotlight.cpp:67) */
+    float frame_t[3];
+    float cos_theta_max;     /* directional: cos(degToRad(angle)) (directionalLight.cpp:92) */
+    float frame_n[3];
+    float pad;
+} nh_emitter_ext;
 
 /* PerspectiveCamera after update() (src/cameras/perspective.cpp:48-96). Row-major 4x4. */
 typedef struct nh_camera {
@@ -230,6 +247,9 @@ typedef struct nh_scene_desc {
     uint64_t n_texels;            /* RGBA texels of every png texture, 4 floats each */
     const float *texels;
     float normals_direction[3];   /* NH_INTEGRATOR_NORMALS: its `direction` point [0, 0, 1] (normals.cpp:10-12) */
+    /* Appended (clients that fill the fields above by name compile unchanged): n_emitters entries, or NULL when the
+       scene has no spot / directional light */
+    const nh_emitter_ext *emitter_ext;
 } nh_scene_desc;
 
 /* ---- BVH in the reference's own layout (include/nori/bvh.h:127-165) ---- */
@@ -460,6 +480,20 @@ int nh_denoise_image(nh_ctx *ctx, float *rgbw, int32_t width, int32_t height, in
 enum { NH_BSDF_QUERY_EVAL = 0, NH_BSDF_QUERY_SAMPLE = 1 };
 int nh_bsdf_query(nh_ctx *ctx, const nh_bsdf *bsdf, const float *albedo, int32_t mode, int32_t n, const float *wi,
                   const float *wo, const float *sample, float *wo_out, float *value, float *pdf, int32_t *measure);
+/* Emitter queries on the device, by the emitter_sample / emitter_eval / emitter_pdf device functions the render
+ * kernels call: emitter `emitter` (any NH_EMITTER_* type) of the uploaded scene, n queries, one lane each.
+ *   NH_EMITTER_QUERY_SAMPLE  in: ref (3n), sample (2n floats). out: NH_EMITTER_QUERY_SAMPLE_STRIDE floats per query:
+ *                            [0..2] the sample's weight (value / pdf), [3..5] wi, [6] pdf(ref, p, n, wi),
+ *                            [7..9] shadow ray origin, [10..12] its direction, [13] mint, [14] maxt, [15] 0
+ *   NH_EMITTER_QUERY_EVAL    in: ref (3n), sample = NH_EMITTER_QUERY_IN_STRIDE floats per query: [0..2] wi,
+ *   NH_EMITTER_QUERY_PDF         [3..5] the point p on the light, [6..8] its normal n (p and n are read for area
+ *                                lights only). out: 3 floats per query (eval's value), 1 float per query (pdf)
+ * Needs an uploaded scene (nh_upload_scene; no BVH). */
+enum { NH_EMITTER_QUERY_SAMPLE = 0, NH_EMITTER_QUERY_EVAL = 1, NH_EMITTER_QUERY_PDF = 2 };
+#define NH_EMITTER_QUERY_SAMPLE_STRIDE 16
+#define NH_EMITTER_QUERY_IN_STRIDE 9
+int nh_emitter_query(nh_ctx *ctx, uint32_t emitter, int32_t mode, int32_t n, const float *ref, const float *sample,
+                     float *out);
 const char *nh_last_error(const nh_ctx *ctx);
 
 #ifdef __cplusplus

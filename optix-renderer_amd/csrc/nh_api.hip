@@ -144,7 +144,8 @@ struct nh_ctx {
     std::vector<int> shape_bsdf_type;
     std::vector<int> shape_bsdf_real;  // NH_BSDF_* of each shape
     int n_bsdf_types = 0;              // distinct BSDF types in the scene
-    bool disney = false;               // a Disney BSDF: the scene renders with the nh_disney:: kernels (NH_LAUNCH)
+    bool disney = false;               // a Disney BSDF, or a spot / directional light: the scene renders with the
+                                       // nh_disney:: kernels (NH_LAUNCH)
     bool specular = false;             // a mirror or dielectric BSDF: long discrete chains, long chunk tails
     bool textured = false;             // a BSDF with an albedo texture
     bool normal_mapped = false;        // a shape with a normal map (the full bounce / tail bodies' NMAP instantiation)
@@ -455,7 +456,9 @@ static bool nee_finite(const nh_scene_desc *d) {
     auto fin = [](float x) { return std::fabs(x) < 1e15f; };
     for (uint32_t i = 0; i < d->n_emitters; ++i) {
         const nh_emitter &e = d->emitters[i];
-        if (e.type == NH_EMITTER_POINT) return false;
+        // (point and spot lights divide by the squared distance to the shading point; a directional light is left
+        // out with them, conservatively: nobody has shown its sample finite at every discrete-BSDF point)
+        if (e.type != NH_EMITTER_AREA && e.type != NH_EMITTER_ENVMAP) return false;
         for (int k = 0; k < 3; ++k)
             if (!std::isfinite(e.radiance[k])) return false;
     }
@@ -609,8 +612,11 @@ int nh_upload_scene(nh_ctx *c, const nh_scene_desc *d) {
         o.intensity = t.intensity;
     }
     std::vector<DEmitter> de(d->n_emitters);
+    std::vector<nhd::DEmitterExt> dx;  // spot / directional lights: n_emitters records (else empty)
     for (uint32_t i = 0; i < d->n_emitters; ++i) {
         const nh_emitter &e = d->emitters[i];
+        if (e.type < NH_EMITTER_AREA || e.type > NH_EMITTER_DIRECTIONAL)
+            return fail(c, "unknown emitter type"), NH_ERR_INVALID;
         if (e.type == NH_EMITTER_ENVMAP && (int32_t)i != d->envmap)
             return fail(c, "only one environment map per scene is supported"), NH_ERR_UNSUPPORTED;
         DEmitter &o = de[i];
@@ -619,6 +625,18 @@ int nh_upload_scene(nh_ctx *c, const nh_scene_desc *d) {
         o.shape = e.shape;
         o.lr = e.radiance[0]; o.lg = e.radiance[1]; o.lb = e.radiance[2];
         o.px = e.position[0]; o.py = e.position[1]; o.pz = e.position[2];
+        if (e.type == NH_EMITTER_SPOT || e.type == NH_EMITTER_DIRECTIONAL) {
+            if (!d->emitter_ext) return fail(c, "spot / directional emitter without emitter_ext"), NH_ERR_INVALID;
+            const nh_emitter_ext &x = d->emitter_ext[i];
+            float len2 = 0.f;
+            for (int k = 0; k < 3; ++k) len2 += x.direction[k] * x.direction[k];
+            if (!std::isfinite(len2) || !(len2 > 0.f))
+                return fail(c, "spot / directional emitter with a zero or non-finite direction"), NH_ERR_INVALID;
+            static_assert(sizeof(nh_emitter_ext) == sizeof(nhd::DEmitterExt), "nh_emitter_ext is DEmitterExt's layout");
+            if (dx.empty()) dx.resize(d->n_emitters);  // (zero records for the other emitters: never read)
+            std::memcpy(&dx[i], &x, sizeof(x));
+            o.shape = (int)i;  // the light's DScene::emitter_ext entry
+        }
     }
     nhd::DScene &S = c->S;
     std::memset(&S, 0, sizeof(S));
@@ -628,6 +646,7 @@ int nh_upload_scene(nh_ctx *c, const nh_scene_desc *d) {
     if ((rc = upload(c, c->scene_bufs, db.data(), db.size(), &S.bsdfs))) return rc;
     if ((rc = upload(c, c->scene_bufs, de.data(), de.size(), &S.emitters))) return rc;
     if ((rc = upload(c, c->scene_bufs, d->emitter_cdf, (size_t)d->n_emitters + 1, &S.emitter_cdf))) return rc;
+    if (!dx.empty() && (rc = upload(c, c->scene_bufs, dx.data(), dx.size(), &S.emitter_ext))) return rc;
     if ((rc = upload(c, c->scene_bufs, d->V, 3 * nv, &S.V))) return rc;
     if ((rc = upload(c, c->scene_bufs, d->N, 3 * nv, &S.N))) return rc;
     if ((rc = upload(c, c->scene_bufs, d->UV, 2 * nv, &S.UV))) return rc;
@@ -771,6 +790,8 @@ int nh_upload_scene(nh_ctx *c, const nh_scene_desc *d) {
         }
     for (int t : c->shape_bsdf_real) c->shape_bsdf_type.push_back(t == NH_BSDF_DISNEY ? disney_key : t);
     c->disney = (types & (1u << NH_BSDF_DISNEY)) != 0;
+    // a spot / directional light takes the same kernel set: only it has their branches (nh_device.h kExtLights)
+    c->disney = c->disney || !dx.empty();
     c->n_bsdf_types = __builtin_popcount(types);
     c->specular = (types & ((1u << NH_BSDF_MIRROR) | (1u << NH_BSDF_DIELECTRIC))) != 0;
     // any BSDF with an albedo texture or shape with a normal map (wf_bounce_rr's lean instantiation has no lookup)
@@ -2379,6 +2400,54 @@ int nh_bsdf_query(nh_ctx *c, const nh_bsdf *b, const float *albedo, int32_t mode
     std::memcpy(value, host.data() + 3 * sn, 3 * sn * sizeof(float));
     std::memcpy(pdf, host.data() + 6 * sn, sn * sizeof(float));
     if (measure) std::memcpy(measure, host.data() + 7 * sn, sn * sizeof(float));
+    return NH_OK;
+}
+
+int nh_emitter_query(nh_ctx *c, uint32_t emitter, int32_t mode, int32_t n, const float *ref, const float *sample,
+                     float *out) {
+    if (!c) return NH_ERR_INVALID;
+    if (n < 0 || !ref || !sample || !out) return fail(c, "nh_emitter_query: null argument"), NH_ERR_INVALID;
+    if (mode < NH_EMITTER_QUERY_SAMPLE || mode > NH_EMITTER_QUERY_PDF)
+        return fail(c, "nh_emitter_query: unknown mode"), NH_ERR_INVALID;
+    if (!c->has_scene) return fail(c, "nh_emitter_query: no scene uploaded"), NH_ERR_STATE;
+    if (emitter >= c->h_emitters.size()) return fail(c, "nh_emitter_query: emitter index out of range"), NH_ERR_INVALID;
+    const nhd::DEmitter &e = c->h_emitters[emitter];
+    if (e.type == NH_EMITTER_AREA && (e.shape < 0 || (size_t)e.shape >= c->h_shapes.size()))
+        return fail(c, "nh_emitter_query: area light without a valid shape"), NH_ERR_INVALID;
+    const size_t sn = (size_t)n;
+    if (mode == NH_EMITTER_QUERY_SAMPLE)  // (the CDF searches of the area and envmap samples index by it)
+        for (size_t i = 0; i < 2 * sn; ++i)
+            if (!(sample[i] >= 0.f && sample[i] < 1.f))
+                return fail(c, "nh_emitter_query: sample outside [0, 1)"), NH_ERR_INVALID;
+    if (n == 0) return NH_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc_ = pipeline_drain(c)) return rc_;
+    std::vector<void *> bufs;  // freed on every return
+    struct Free {
+        std::vector<void *> &v;
+        ~Free() { free_all(v); }
+    } guard{bufs};
+    // the scene record as nh_upload_scene left it (the device copy the render kernels read exists only once a BVH is
+    // uploaded; the emitter functions read no BVH field)
+    const nhd::DScene *d_s = nullptr;
+    if (int rc = upload(c, bufs, &c->S, 1, &d_s)) return rc;
+    nh_disney::nh::EmitterQuery q;
+    q.emitter = (int)emitter;
+    q.mode = mode;
+    q.n = n;
+    const size_t in_stride = mode == NH_EMITTER_QUERY_SAMPLE ? 2 : NH_EMITTER_QUERY_IN_STRIDE;
+    const size_t out_stride = mode == NH_EMITTER_QUERY_SAMPLE ? NH_EMITTER_QUERY_SAMPLE_STRIDE
+                                                              : (mode == NH_EMITTER_QUERY_EVAL ? 3 : 1);
+    if (int rc = upload(c, bufs, ref, 3 * sn, &q.ref)) return rc;
+    if (int rc = upload(c, bufs, sample, in_stride * sn, &q.in)) return rc;
+    void *d_out = nullptr;
+    HIP_TRY(c, hipMalloc(&d_out, out_stride * sn * sizeof(float)));
+    bufs.push_back(d_out);
+    q.out = static_cast<float *>(d_out);
+    nh_disney::nh::launch_emitter_query(d_s, q, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(out, d_out, out_stride * sn * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return NH_OK;
 }
 

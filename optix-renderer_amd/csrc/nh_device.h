@@ -175,7 +175,13 @@ constexpr bool kDisney = true;
 #else
 constexpr bool kDisney = false;
 #endif
-enum : int { EMITTER_AREA = 0, EMITTER_POINT = 1, EMITTER_ENVMAP = 2 };
+enum : int { EMITTER_AREA = 0, EMITTER_POINT = 1, EMITTER_ENVMAP = 2, EMITTER_SPOT = 3, EMITTER_DIRECTIONAL = 4 };
+// The spot / directional branches of emitter_sample / emitter_eval / emitter_pdf (nh_shade.h) exist in the same
+// translation units as the Disney branch -- the -DNH_DISNEY copies of the render kernels and the query kernels --
+// which nh_upload_scene also chooses for a scene with one of those lights: every other scene launches kernels
+// compiled without them, unchanged (inlined into the general kernels they cost wf_bounce_rr 32 B/lane of scratch,
+// profiles/lights_kernel_resources.txt).
+constexpr bool kExtLights = kDisney;
 enum : int { M_UNKNOWN = 0, M_SOLID_ANGLE = 1, M_DISCRETE = 2 };
 
 struct alignas(16) DShape {
@@ -230,10 +236,20 @@ struct alignas(16) DTex {
     float pad;
 };
 struct alignas(16) DEmitter {
-    int type, shape;
+    int type, shape;  // shape: the owning shape of an area light; spot / directional: the light's DScene::emitter_ext entry
     float lr, lg, lb;
     float px, py, pz;
 };
+// SpotLight / DirectionalLight (spotlight.cpp, directionalLight.cpp): what they hold beyond a DEmitter, which stays 32
+// bytes for the kernels that stage the emitter table to LDS. In global memory (DScene::emitter_ext), read only by the
+// spot / directional branches of the emitter functions (nh_shade.h). nh_emitter_ext's layout.
+struct alignas(16) DEmitterExt {
+    float dx, dy, dz, cos_total;    // m_direction; spot: cos(degToRad(totalwidth / 2))
+    float sx, sy, sz, cos_falloff;  // m_coord.s; spot: cos(degToRad(falloffstart))
+    float tx, ty, tz, cos_max;      // m_coord.t; directional: cos(degToRad(angle))
+    float nx, ny, nz, pad;          // m_coord.n
+};
+static_assert(sizeof(DEmitter) == 32 && sizeof(DEmitterExt) == 64, "emitter records");
 
 struct DScene {
     // BVH: 4 float4 per inner node, 3 float4 per primitive in leaf order
@@ -293,6 +309,8 @@ struct DScene {
     int nee_finite;
     // isolated dielectric spheres the BVH upload marked (nh_traverse.h trace_next; 0: no ray tries the shortcut)
     int iso_spheres;
+    // spot / directional lights: n_emitters records indexed by DEmitter::shape (nullptr: the scene has neither)
+    const DEmitterExt *emitter_ext;
 };
 
 NHD F3 ldv(const float *a, uint32_t i) { return f3(a[3 * i], a[3 * i + 1], a[3 * i + 2]); }

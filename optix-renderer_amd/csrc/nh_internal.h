@@ -273,5 +273,14 @@ struct BsdfQuery {
     int *measure;
 };
 void launch_bsdf_query(const BsdfQuery &q, hipStream_t st);
+// nh_emitter_query's kernel (nh_emitter_query.hip): emitter_sample (mode 0), emitter_eval (1) or emitter_pdf (2) of
+// S.emitters[emitter], n queries. in: 2 floats per query (mode 0: the sample) or NH_EMITTER_QUERY_IN_STRIDE (wi, p, n);
+// out: NH_EMITTER_QUERY_SAMPLE_STRIDE, 3 or 1 floats per query
+struct EmitterQuery {
+    int emitter, mode, n;
+    const float *ref, *in;
+    float *out;
+};
+void launch_emitter_query(const nhd::DScene *S, const EmitterQuery &q, hipStream_t st);
 }  // namespace nh
 }  // namespace nh_disney

@@ -215,7 +215,53 @@ __device__ __forceinline__ float env_pdf(const DScene &S, F3 wi) {  // EnvMap::p
     return lum * S.env_norm / sphere_pdf * (float)(unsigned)S.env_h * (float)(unsigned)S.env_w;
 }
 
-// AreaEmitter / PointLight / EnvMap (src/emitters/arealight.cpp:58-125, pointlight.cpp:47-78)
+// SpotLight::falloff (spotlight.cpp:184-203) of the world direction w (from the light towards the receiver): the cosine
+// is the z of m_coord.toLocal(w).normalized(); std::pow(float, int) is the double pow, rounded on return
+__device__ __forceinline__ float spot_falloff(const DEmitterExt &x, F3 w) {
+    const F3 l = normalized(f3(dot(w, f3(x.sx, x.sy, x.sz)), dot(w, f3(x.tx, x.ty, x.tz)), dot(w, f3(x.nx, x.ny, x.nz))));
+    const float c = l.z;
+    if (c < x.cos_total) return 0.f;
+    if (c >= x.cos_falloff) return 1.f;
+    const float delta = (c - x.cos_total) / (x.cos_falloff - x.cos_total);
+    const double d2 = (double)delta * (double)delta;
+    return (float)(d2 * d2);
+}
+// SpotLight::eval (spotlight.cpp:65-72) with the intensity i folded into e's radiance at load: i * falloff(-wi) / |ref - position|^2
+__device__ __forceinline__ F3 spot_eval(const DScene &S, const DEmitter &e, F3 ref, F3 wi) {
+    const DEmitterExt x = S.emitter_ext[e.shape];
+    const F3 dd = sub(ref, f3(e.px, e.py, e.pz));
+    const float q = dot(dd, dd), f = spot_falloff(x, neg(wi));
+    return f3(e.lr * f / q, e.lg * f / q, e.lb * f / q);
+}
+// DirectionalLight::pdf (directionalLight.cpp:133-138): squareToUniformSphereCapPdf (warp.cpp:68-72) of
+// m_coord.toLocal(-wi) -- zero for a unit vector at or below the cap's rim, the cap's uniform density everywhere else
+__device__ __forceinline__ float directional_pdf(const DEmitterExt &x, F3 wi) {
+    const F3 w = neg(wi);
+    const F3 l = f3(dot(w, f3(x.sx, x.sy, x.sz)), dot(w, f3(x.tx, x.ty, x.tz)), dot(w, f3(x.nx, x.ny, x.nz)));
+    return (fabsf(dot(l, l) - 1.0f) < kEps && l.z <= x.cos_max) ? 0.0f : 1.0f / (2.0f * kPi * (1.0f - x.cos_max));
+}
+// DirectionalLight::sample (directionalLight.cpp:90-106): wi from squareToUniformSphereCap (warp.cpp:58-66) about
+// -direction; the shadow ray starts at ref and runs along +wi to infinity (Ray3f(ref, wi): mint Epsilon, maxt inf)
+__device__ __forceinline__ F3 directional_sample(const DScene &S, const DEmitter &e, F3 ref, float sx, float sy,
+                                              F3 &wi_out, float &pdf_out) {
+    const DEmitterExt x = S.emitter_ext[e.shape];
+    const float z = sx * (1.0f - x.cos_max) + x.cos_max;
+    const float r = f_sqrt(1.0f - z * z);
+    const float theta = sy * 2.0f * kPi;
+    float st, ct;
+    f_sincos(theta, st, ct);
+    const F3 v = f3(r * ct, r * st, z);
+    const F3 world = add(add(scl(v.x, f3(x.sx, x.sy, x.sz)), scl(v.y, f3(x.tx, x.ty, x.tz))), scl(v.z, f3(x.nx, x.ny, x.nz)));
+    const F3 wi = neg(normalized(world));
+    wi_out = wi;
+    const float pdf = directional_pdf(x, wi);
+    pdf_out = pdf;
+    if (pdf < kEps) return f3(0, 0, 0);
+    return f3(e.lr / pdf, e.lg / pdf, e.lb / pdf);
+}
+
+// AreaEmitter / PointLight / EnvMap / SpotLight / DirectionalLight (src/emitters/arealight.cpp:58-125,
+// pointlight.cpp:47-78, environmentmap.cpp, spotlight.cpp:53-77, directionalLight.cpp:90-138)
 // AREA_MESH (the diffuse area-light instantiations of the RR-ahead kernels, nh_wavefront.hip): the caller knows e is an
 // area light on a mesh with an emit_faces record, so only that path is compiled -- the same operations on it.
 // shapes: the table e.shape indexes (S.shapes, or a copy of it)
@@ -227,7 +273,8 @@ __device__ __forceinline__ float emitter_pdf(const DScene &S, const DShape *shap
         return shapes[e.shape].pdf_norm * dot(sub(p, ref), sub(p, ref)) / fabsf(dot(n, neg(wi)));
     }
     if (e.type == EMITTER_ENVMAP) return env_pdf(S, wi);
-    if (e.type == EMITTER_POINT) return 1.f;
+    if (e.type == EMITTER_POINT || (kExtLights && e.type == EMITTER_SPOT)) return 1.f;
+    if (kExtLights && e.type == EMITTER_DIRECTIONAL) return directional_pdf(S.emitter_ext[e.shape], wi);
     if (dot(n, neg(wi)) < 0.f) return 0.f;
     const DShape sh = shapes[e.shape];
     // Sphere::pdfSurface: std::pow(1.f / r, 2) (double, exact square) * (0.25f / M_PI)
@@ -248,6 +295,14 @@ __device__ __forceinline__ F3 emitter_eval(const DEmitter &e, F3 ref, F3 n, F3 w
     }
     if (dot(n, neg(wi)) < 0.f) return f3(0, 0, 0);
     return f3(e.lr, e.lg, e.lb);
+}
+// The same for any emitter type. No ray ends on a spot or directional light (they have no shape), so the kernels
+// evaluate those two only through their light samples; nh_emitter_query evaluates every type through this.
+__device__ __forceinline__ F3 emitter_eval(const DScene &S, const DEmitter &e, F3 ref, F3 n, F3 wi) {
+    if (kExtLights && e.type == EMITTER_SPOT) return spot_eval(S, e, ref, wi);
+    if (kExtLights && e.type == EMITTER_DIRECTIONAL) return f3(e.lr, e.lg, e.lb);  // DirectionalLight::eval: m_radiance
+    if (e.type == EMITTER_ENVMAP) return env_eval(S, wi);
+    return emitter_eval(e, ref, n, wi);
 }
 
 struct ESample {
@@ -280,7 +335,8 @@ __device__ __forceinline__ F3 emitter_sample(const DScene &S, const ST &T, const
         const F3 ev = env_eval(S, es.wi);
         return f3(ev.x / pdf, ev.y / pdf, ev.z / pdf);
     }
-    if (!AREA_MESH && e.type == EMITTER_POINT) {
+    if (!AREA_MESH && (e.type == EMITTER_POINT || (kExtLights && e.type == EMITTER_SPOT))) {
+        // SpotLight::sample (spotlight.cpp:53-63) is PointLight::sample with its own eval
         F3 pos = f3(e.px, e.py, e.pz);
         F3 rp = sub(ref, pos);
         es.so = pos;
@@ -290,7 +346,19 @@ __device__ __forceinline__ F3 emitter_sample(const DScene &S, const ST &T, const
         es.wi = normalized(sub(pos, ref));
         es.p = f3(0, 0, 0);
         es.n = f3(0, 0, 0);
+        if (kExtLights && e.type == EMITTER_SPOT) return spot_eval(S, e, ref, es.wi);
         return emitter_eval(e, ref, es.n, es.wi);
+    }
+    if (!AREA_MESH && kExtLights && e.type == EMITTER_DIRECTIONAL) {
+        float pdf;
+        const F3 col = directional_sample(S, e, ref, sx, sy, es.wi, pdf);
+        es.so = ref;
+        es.sd = es.wi;
+        es.smint = kEps;
+        es.smaxt = INFINITY;
+        es.p = f3(0, 0, 0);
+        es.n = f3(0, 0, 0);
+        return col;
     }
     const DShape sh = T.shapes[e.shape];
     F3 p, n;

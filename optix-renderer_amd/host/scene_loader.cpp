@@ -221,6 +221,7 @@ struct SceneData {
     std::vector<nh_shape> shapes;
     std::vector<nh_bsdf> bsdfs;
     std::vector<nh_emitter> emitters;
+    std::vector<nh_emitter_ext> emitter_ext;  // empty, or one per emitter (spot / directional lights fill theirs)
     std::vector<float> emitter_cdf;
     int32_t envmap = -1;
     std::vector<float> V, N, UV, T, BT;
@@ -887,6 +888,33 @@ void build_envmap(const Obj &o, const std::string &base_dir, SceneData &sd, nh_e
     }
 }
 
+// degToRad (common.h:218, with Nori's float M_PI) and std::cos(float): the float libm's result, taken as the
+// correctly rounded one (as the device code's transcendentals, nh_device.h)
+float deg_to_rad(float v) { return v * (kPiF / 180.0f); }
+float cos_float(float x) { return (float)std::cos((double)x); }
+
+// nh_emitter_ext's direction and Frame(n) (frame.h, coordinateSystem: common.cpp:292-306; nh_device.h frame_from_n)
+void set_frame(nh_emitter_ext &x, V3 dir, V3 n) {
+    V3 t;
+    if (std::fabs(n.x) > std::fabs(n.y)) {
+        const float inv_len = 1.0f / std::sqrt(n.x * n.x + n.z * n.z);
+        t = v3(n.z * inv_len, 0.0f, -n.x * inv_len);
+    } else {
+        const float inv_len = 1.0f / std::sqrt(n.y * n.y + n.z * n.z);
+        t = v3(0.0f, n.z * inv_len, -n.y * inv_len);
+    }
+    const V3 s = cross3(t, n);
+    x.direction[0] = dir.x; x.direction[1] = dir.y; x.direction[2] = dir.z;
+    x.frame_s[0] = s.x; x.frame_s[1] = s.y; x.frame_s[2] = s.z;
+    x.frame_t[0] = t.x; x.frame_t[1] = t.y; x.frame_t[2] = t.z;
+    x.frame_n[0] = n.x; x.frame_n[1] = n.y; x.frame_n[2] = n.z;
+}
+// the side record of the emitter about to be appended to sd.emitters (entries of other emitters stay zero)
+void set_emitter_ext(SceneData &sd, const nh_emitter_ext &x) {
+    sd.emitter_ext.resize(sd.emitters.size() + 1);
+    sd.emitter_ext.back() = x;
+}
+
 void build_scene(const Obj &scene, const std::string &base_dir, SceneData &sd) {
     bool have_camera = false, have_integrator = false, have_sampler = false;
     set_filter(sd.filter, 0, 2.0f, 0.5f, 1.0f / 3.0f, 1.0f / 3.0f);
@@ -1014,6 +1042,40 @@ void build_scene(const Obj &scene, const std::string &base_dir, SceneData &sd) {
                 if (sd.envmap >= 0) throw SceneError("only one environment map per scene is supported");
                 build_envmap(ch, base_dir, sd, em);
                 sd.envmap = (int32_t)sd.emitters.size();
+            } else if (ch.type == "spot") {  // SpotLight (spotlight.cpp:14-23, :50, :65-69)
+                em.type = NH_EMITTER_SPOT;
+                const V3 p = ch.props.get_point("position", v3(0, 0, 0));
+                const V3 dir = normalized(ch.props.get_vector("direction", v3(0, 0, 0)));
+                const V3 pw = ch.props.get_color("power", v3(0, 0, 0));
+                const float falloff_start = ch.props.get_float("falloffstart");
+                const float total_width = ch.props.get_float("totalwidth");
+                // (the reference normalizes a zero vector here and renders NaN: nothing to reproduce)
+                if (!(dot3(dir, dir) > 0.f) || !std::isfinite(dot3(dir, dir)))
+                    throw SceneError("spot emitter: the direction must be a finite non-zero vector");
+                em.position[0] = p.x; em.position[1] = p.y; em.position[2] = p.z;
+                nh_emitter_ext x{};
+                x.cos_falloff_start = cos_float(deg_to_rad(falloff_start));
+                x.cos_total_width = cos_float(deg_to_rad(total_width / 2.f));
+                // update(): m_radiance = m_power / 2.f / M_PI (M_PI is Nori's float constant, common.h:61); eval():
+                // i = m_radiance / (1.f - .5f * (cosTotalWidth + cosFalloffStart)), folded here
+                const float norm = 1.f - .5f * (x.cos_total_width + x.cos_falloff_start);
+                em.radiance[0] = pw.x / 2.f / kPiF / norm;
+                em.radiance[1] = pw.y / 2.f / kPiF / norm;
+                em.radiance[2] = pw.z / 2.f / kPiF / norm;
+                set_frame(x, dir, normalized(dir));  // m_coord = Frame(m_direction.normalized())
+                set_emitter_ext(sd, x);
+            } else if (ch.type == "directional") {  // DirectionalLight (directionalLight.cpp:32-39)
+                em.type = NH_EMITTER_DIRECTIONAL;
+                em.light_prob = 1.f;  // its constructor never reads lightWeight (emitter.h:151)
+                const V3 dir = normalized(ch.props.get_vector("direction", v3(0, 0, 1)));
+                const V3 rad = ch.props.get_color("radiance", v3(0, 0, 0));
+                if (!(dot3(dir, dir) > 0.f) || !std::isfinite(dot3(dir, dir)))
+                    throw SceneError("directional emitter: the direction must be a finite non-zero vector");
+                em.radiance[0] = rad.x; em.radiance[1] = rad.y; em.radiance[2] = rad.z;
+                nh_emitter_ext x{};
+                x.cos_theta_max = cos_float(deg_to_rad(ch.props.get_float("angle", 1.f)));
+                set_frame(x, dir, dir);  // m_coord = Frame(m_direction)
+                set_emitter_ext(sd, x);
             } else {
                 throw SceneError("emitter \"" + ch.type + "\" is not supported yet");
             }
@@ -1040,6 +1102,7 @@ void build_scene(const Obj &scene, const std::string &base_dir, SceneData &sd) {
     }
     if (!have_integrator) throw SceneError("No integrator was specified!");
     if (!have_camera) throw SceneError("No camera was specified!");
+    if (!sd.emitter_ext.empty()) sd.emitter_ext.resize(sd.emitters.size());  // one entry per emitter
     // Scene::update: emitter DiscretePDF
     sd.emitter_cdf.assign(1, 0.0f);
     for (auto &e : sd.emitters) sd.emitter_cdf.push_back(sd.emitter_cdf.back() + e.light_prob);
@@ -1102,6 +1165,7 @@ void fill_desc(const SceneData &sd, nh_scene_desc *d) {
     d->n_emitters = (uint32_t)sd.emitters.size();
     d->emitters = sd.emitters.data();
     d->emitter_cdf = sd.emitter_cdf.data();
+    d->emitter_ext = sd.emitter_ext.empty() ? nullptr : sd.emitter_ext.data();
     d->envmap = sd.envmap;
     d->denoiser = sd.denoiser;
     d->n_vertices = (uint32_t)(sd.V.size() / 3);

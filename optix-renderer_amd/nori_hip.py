@@ -33,6 +33,9 @@ BSDF_DIFFUSE, BSDF_MIRROR, BSDF_DIELECTRIC, BSDF_MICROFACET = 0, 1, 2, 3
 BSDF_DISNEY = 4  # disney.cpp
 BSDF_QUERY_EVAL, BSDF_QUERY_SAMPLE = 0, 1
 EMITTER_AREA, EMITTER_POINT, EMITTER_ENVMAP = 0, 1, 2
+EMITTER_SPOT, EMITTER_DIRECTIONAL = 3, 4  # spotlight.cpp, directionalLight.cpp
+EMITTER_QUERY_SAMPLE, EMITTER_QUERY_EVAL, EMITTER_QUERY_PDF = 0, 1, 2
+EMITTER_QUERY_SAMPLE_STRIDE, EMITTER_QUERY_IN_STRIDE = 16, 9
 INTEGRATOR_PATH_MIS, INTEGRATOR_PATH_MATS, INTEGRATOR_DIRECT_EMS, INTEGRATOR_DIRECT_MATS, INTEGRATOR_DIRECT_MIS = 0, 1, 2, 3, 4
 INTEGRATOR_DIRECT = 5  # the point-light `direct` integrator of scenes/pa1 (direct.cpp)
 INTEGRATOR_NORMALS = 6  # the `normals` integrator of the normal-map scenes (normals.cpp)
@@ -82,6 +85,11 @@ class nh_emitter(C.Structure):
                 ("position", _f * 3), ("pad", _f)]
 
 
+class nh_emitter_ext(C.Structure):
+    _fields_ = [("direction", _f * 3), ("cos_total_width", _f), ("frame_s", _f * 3), ("cos_falloff_start", _f),
+                ("frame_t", _f * 3), ("cos_theta_max", _f), ("frame_n", _f * 3), ("pad", _f)]
+
+
 class nh_camera(C.Structure):
     _fields_ = [("width", _i32), ("height", _i32), ("sample_to_camera", _f * 16), ("camera_to_world", _f * 16),
                 ("inv_output_size", _f * 2), ("near_clip", _f), ("far_clip", _f), ("lens_radius", _f),
@@ -127,7 +135,7 @@ class nh_scene_desc(C.Structure):
                 ("UV", _fp), ("T", _fp), ("BT", _fp), ("n_faces", _u32), ("F", _u32p), ("n_area_cdf", _u32),
                 ("area_cdf", _fp), ("env", nh_envmap), ("denoiser", nh_denoiser), ("n_textures", _u32),
                 ("textures", C.POINTER(nh_texture)), ("n_texels", C.c_uint64), ("texels", _fp),
-                ("normals_direction", _f * 3)]
+                ("normals_direction", _f * 3), ("emitter_ext", C.POINTER(nh_emitter_ext))]
 
 
 class nh_bvh_node(C.Structure):
@@ -227,6 +235,7 @@ _sig("nh_reduce_framebuffers", _i32, C.POINTER(_vp), _i32, _i32)
 _sig("nh_denoise", _i32, _vp, C.POINTER(nh_denoiser))
 _sig("nh_denoise_image", _i32, _vp, _fp, _i32, _i32, _i32, C.POINTER(nh_denoiser))
 _sig("nh_bsdf_query", _i32, _vp, C.POINTER(nh_bsdf), _fp, _i32, _i32, _fp, _fp, _fp, _fp, _fp, _fp, C.POINTER(_i32))
+_sig("nh_emitter_query", _i32, _vp, _u32, _i32, _i32, _fp, _fp, _fp)
 _sig("nh_last_error", C.c_char_p, _vp)
 
 lib = _lib
@@ -524,6 +533,40 @@ class Context:
                                     _fptr(wi), None, _fptr(sample), _fptr(out["wo"]), _fptr(out["value"]),
                                     _fptr(out["pdf"]), out["measure"].ctypes.data_as(C.POINTER(_i32)))
         self._check(rc, "bsdf_query")
+        return out
+
+    def emitter_query(self, emitter: int, ref: np.ndarray, sample: np.ndarray = None, wi: np.ndarray = None,
+                      p: np.ndarray = None, n: np.ndarray = None, mode: int = None) -> dict:
+        """nh_emitter_query: queries of emitter `emitter` of the uploaded scene by the render kernels' own device
+        functions. ref: (m, 3) reference points. With sample (m, 2): emitter_sample -> {"value": the sample's weight
+        (m, 3), "wi": (m, 3), "pdf": (m,), "o" / "d": the shadow ray (m, 3), "mint" / "maxt": (m,)}. With wi (m, 3)
+        instead (and, for area lights, the point p on the light and its normal n): {"value": eval (m, 3),
+        "pdf": (m,)}; mode = EMITTER_QUERY_EVAL / EMITTER_QUERY_PDF runs only that one."""
+        if (sample is None) == (wi is None):
+            raise ValueError("emitter_query: give either sample (sample) or wi (eval and pdf)")
+        ref = np.ascontiguousarray(ref, dtype=np.float32).reshape(-1, 3)
+        m = len(ref)
+
+        def call(md, inp, out):
+            self._check(_lib.nh_emitter_query(self._h, emitter, md, m, _fptr(ref), _fptr(inp), _fptr(out)),
+                        "emitter_query")
+            return out
+        if sample is not None:
+            sample = np.ascontiguousarray(sample, dtype=np.float32).reshape(m, 2)
+            o = call(EMITTER_QUERY_SAMPLE, sample, np.zeros((m, EMITTER_QUERY_SAMPLE_STRIDE), np.float32))
+            return {"value": o[:, 0:3].copy(), "wi": o[:, 3:6].copy(), "pdf": o[:, 6].copy(), "o": o[:, 7:10].copy(),
+                    "d": o[:, 10:13].copy(), "mint": o[:, 13].copy(), "maxt": o[:, 14].copy()}
+        inp = np.zeros((m, EMITTER_QUERY_IN_STRIDE), np.float32)
+        inp[:, 0:3] = np.asarray(wi, np.float32).reshape(m, 3)
+        if p is not None:
+            inp[:, 3:6] = np.asarray(p, np.float32).reshape(m, 3)
+        if n is not None:
+            inp[:, 6:9] = np.asarray(n, np.float32).reshape(m, 3)
+        out = {}
+        if mode in (None, EMITTER_QUERY_EVAL):
+            out["value"] = call(EMITTER_QUERY_EVAL, inp, np.zeros((m, 3), np.float32))
+        if mode in (None, EMITTER_QUERY_PDF):
+            out["pdf"] = call(EMITTER_QUERY_PDF, inp, np.zeros(m, np.float32))
         return out
 
     def trace(self, o: np.ndarray, d: np.ndarray, mint: np.ndarray, maxt: np.ndarray, any_hit=False,
