@@ -32,7 +32,8 @@ __device__ __noinline__ F3 tex_eval(const DTex *texs, const float4 *texels, int 
 #define NH_NMAP_ON true
 #endif
 // shapes: the shape table (S.shapes, or a copy of it)
-template <bool NMAP_ = true>
+// MESH: the caller knows the hit shape is a mesh (the lean head of the trait kernels): no sphere branch
+template <bool NMAP_ = true, bool MESH = false>
 __device__ __forceinline__ void hit_info(const DScene &S, const DShape *shapes, const Traversal &tv, const Hit &h, F3 o,
                                          F3 d, Its &its) {
     constexpr bool NMAP = NMAP_ && NH_NMAP_ON;
@@ -40,7 +41,7 @@ __device__ __forceinline__ void hit_info(const DScene &S, const DShape *shapes, 
     const int shape = __float_as_int(b.w);
     const DShape sh = shapes[shape];
     its.shape = shape;
-    if (sh.type == SHAPE_SPHERE) {
+    if (!MESH && sh.type == SHAPE_SPHERE) {
         its.p = add(o, scl(h.t, d));
         F3 n = normalized(sub(its.p, f3(sh.cx, sh.cy, sh.cz)));
         // uv (two fp64-evaluated transcendentals) only matters to a textured albedo (bsdf_albedo) and a normal map,

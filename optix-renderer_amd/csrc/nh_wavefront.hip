@@ -667,17 +667,33 @@ struct PathV {
 // TRAIT (the diffuse area-light instantiations, see wf_bounce_rr): path_mis with area lights on meshes only -- no
 // path_mats copy, no environment term, no emitter type dispatch; the same operations on the path that is left.
 // T: the scene tables (S, or the staged copies: SceneTables)
-template <bool NMAP = true, bool TRAIT = false, class ST = DScene>
+// LEAN (the bounce kernels, whose next launch recomputes the Intersection from the stored hit): the caller does not
+// read its, and the head itself reads only its.p and its.sh.n, only where the hit shape is an emitter -- so hit_info
+// runs in those lanes alone (in the trait kernels its mesh branch alone: every emitter there is a mesh), on the same
+// values. -DNH_LEAN_HEAD=0 (A/B builds): the Intersection of every hit, as wf_tail_rr and first_vertex need it.
+#ifndef NH_LEAN_HEAD
+#define NH_LEAN_HEAD 1
+#endif
+template <bool NMAP = true, bool TRAIT = false, bool LEAN_ = false, class ST = DScene>
 __device__ __forceinline__ bool shade_head(const DScene &S, const ST &T, const Traversal &tv, PathV &v, const Hit &h,
                                            bool found, float pdfmat, Its &its) {
+    constexpr bool LEAN = LEAN_ && NH_LEAN_HEAD;
     bool have_its = false;
+    int hit_em = 0;  // LEAN: the hit shape's emitter index (the shape id is word 1 .w of the hit's record)
+    if constexpr (LEAN) {
+        hit_em = found ? T.shapes[__float_as_int(tv.prims[3 * h.k + 1].w)].emitter : -1;
+        if (hit_em >= 0) hit_info<NMAP, TRAIT>(S, T.shapes, tv, h, v.org, v.d, its);
+        have_its = true;
+    }
     if (!TRAIT && S.integrator == 1) {  // ---------------- path_mats (path_mats.cpp:16-78)
         if (!found) {  // path_mats.cpp:26-35
             if (S.envmap >= 0) v.li = add(v.li, mulc(v.t, env_eval(S, v.d)));
             return false;
         }
-        hit_info<NMAP>(S, T.shapes, tv, h, v.org, v.d, its);
-        const DShape shape = T.shapes[its.shape];
+        if (!have_its) hit_info<NMAP>(S, T.shapes, tv, h, v.org, v.d, its);
+        DShape shape;
+        if constexpr (LEAN) shape.emitter = hit_em;
+        else shape = T.shapes[its.shape];
         if (shape.emitter >= 0) {
             const F3 wi = normalized(sub(its.p, v.org));
             v.li = add(v.li, mulc(v.t, emitter_eval(T.emitters[shape.emitter], v.org, its.sh.n, wi)));
@@ -695,9 +711,11 @@ __device__ __forceinline__ bool shade_head(const DScene &S, const ST &T, const T
     if (!(v.flags & F_FIRST)) {  // finish the previous bounce (path_mis.cpp:115-140)
         // the MIS probe hit an emitter (:117-133): w_mats from the pdfs of both strategies
         if (!(v.flags & F_ZERO_COL) && found) {
-            hit_info<NMAP>(S, T.shapes, tv, h, v.org, v.d, its);
+            if (!have_its) hit_info<NMAP>(S, T.shapes, tv, h, v.org, v.d, its);
             have_its = true;
-            const int hem = T.shapes[its.shape].emitter;
+            int hem;
+            if constexpr (LEAN) hem = hit_em;
+            else hem = T.shapes[its.shape].emitter;
             if (hem >= 0) {
                 const F3 wim = normalized(sub(its.p, v.org));
                 const float pdfmat_ems =
@@ -712,7 +730,9 @@ __device__ __forceinline__ bool shade_head(const DScene &S, const ST &T, const T
         return false;
     }
     if (!have_its) hit_info<NMAP>(S, T.shapes, tv, h, v.org, v.d, its);
-    const DShape shape = T.shapes[its.shape];
+    DShape shape;
+    if constexpr (LEAN) shape.emitter = hit_em;
+    else shape = T.shapes[its.shape];
     if (shape.emitter >= 0) {  // path_mis.cpp:51-56, ref = ray origin
         const F3 wi = normalized(sub(its.p, v.org));
         v.li = add(v.li, mulc(scl(v.w_mats, v.t), emitter_eval<TRAIT>(T.emitters[shape.emitter], v.org, its.sh.n, wi)));
@@ -1237,8 +1257,9 @@ struct TailClocks {
 // branches and their tex_eval calls cost C1 / C4 2.5 % when present, profiles/round6_ab_nmap.txt)
 // TRAIT: the diffuse area-light body and head; the stream increment stays in its registers over the step instead of
 // being re-derived from the path id (path_of), and the traversals take the guarded fast reciprocal (trace<.., RCP>)
+// LEAN: the caller drops its afterwards (shade_head)
 template <bool ORDERED, bool STATS, bool CLK = false, int G = 1, bool FULL = true, bool NMAP = FULL, bool TRAIT = false,
-          class ST = DScene>
+          bool LEAN = false, class ST = DScene>
 __device__ __forceinline__ bool rr_step(const DScene &S, const ST &T, const Traversal &tv, const WfLaunch &L, PathV &v, Its &its,
                                         Hit &h, uint32_t *stk, int stride, TravStats &st_e, TravStats &st_s,
                                         unsigned long long &q_e, unsigned long long &q_s, TailClocks *clk = nullptr) {
@@ -1299,7 +1320,7 @@ __device__ __forceinline__ bool rr_step(const DScene &S, const ST &T, const Trav
     } else {
         v = path_of(L, o);
     }
-    const bool alive = shade_head<NMAP, TRAIT>(S, T, tv, v, h, found, o.pdfmat, its);
+    const bool alive = shade_head<NMAP, TRAIT, LEAN>(S, T, tv, v, h, found, o.pdfmat, its);
     if constexpr (CLK) {
         if (lead) cs[3] += clock64() - t0;
         if (lead) ++(G > 1 ? clk->coop_bounces : clk->bounces);
@@ -1340,8 +1361,9 @@ __device__ __forceinline__ bool bounce_path(const DScene &S, const ST &T, const 
         load_post_head<NMAP>(S, T, tv, L, L.st.buf[L.in_q], queue_slot(qv.pre, L.seg_cap, q), v, h, its);
     }
     if constexpr (STATS) c_load += clock64() - t_ph;
-    return alive && rr_step<ORDERED, STATS, STATS, 1, FULL, NMAP, TRAIT>(S, T, tv, L, v, its, h, my_stk, NH_BOUNCE_TB,
-                                                                   st_e, st_s, q_e, q_s, &clk);
+    // its is dropped here: the next launch recomputes it from the stored hit (unpack_post_head)
+    return alive && rr_step<ORDERED, STATS, STATS, 1, FULL, NMAP, TRAIT, true>(S, T, tv, L, v, its, h, my_stk,
+                                                                         NH_BOUNCE_TB, st_e, st_s, q_e, q_s, &clk);
 }
 
 // TRAIT, BOUNCE: the diffuse area-light instantiations (launch_wf_bounce_trait), one for bounce 0 and one for the later
