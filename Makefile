@@ -21,8 +21,9 @@ HIP_FLAGS  := -std=c++17 -O3 -fPIC --offload-arch=$(ARCH) $(FP_FLAGS) \
               -Iinclude -I$(PKG)/csrc -Wno-unused-result $(EXTRA_HIP)
 
 HOST_SRC := $(PKG)/host/xml_lite.cpp $(PKG)/host/scene_loader.cpp $(PKG)/host/bvh_build.cpp $(PKG)/host/image_io.cpp \
-            $(PKG)/host/png_decode.cpp $(PKG)/host/hdr_decode.cpp
-HIP_SRC  := $(PKG)/csrc/nh_kernels.hip $(PKG)/csrc/nh_denoise.hip $(PKG)/csrc/nh_splat.hip $(PKG)/csrc/nh_api.hip
+            $(PKG)/host/png_decode.cpp $(PKG)/host/hdr_decode.cpp $(PKG)/host/gpu_layout.cpp
+HIP_SRC  := $(PKG)/csrc/nh_kernels.hip $(PKG)/csrc/nh_denoise.hip $(PKG)/csrc/nh_splat.hip $(PKG)/csrc/nh_api.hip \
+            $(PKG)/csrc/nh_upload.hip $(PKG)/csrc/nh_pipeline.hip
 HOST_OBJ := $(patsubst $(PKG)/host/%.cpp,$(OBJDIR)/host_%.o,$(HOST_SRC))
 # nh_wavefront.hip is compiled as five translation units (-DNH_WF_PART=k, each instantiating its own kernels) so
 # its kernels build in parallel
@@ -32,12 +33,12 @@ HIP_OBJ  := $(patsubst $(PKG)/csrc/%.hip,$(OBJDIR)/hip_%.o,$(HIP_SRC)) \
 # The Disney variant (nh_device.h kDisney): the megakernel file and the shading parts of nh_wavefront.hip compiled once
 # more with -DNH_DISNEY, as namespace nh_disney, plus the Disney-only kernels of nh_disney.hip and the emitter query
 # kernel. It also holds the spot / directional light branches (kExtLights). Scenes without a Disney BSDF or one of
-# those lights never launch these (nh_api.hip NH_LAUNCH). Only what shades is built: parts 0 and 3 (traversal kernels) and
+# those lights never launch these (nh_ctx.h NH_LAUNCH). Only what shades is built: parts 0 and 3 (traversal kernels) and
 # part 4 (the diffuse area-light instantiations) have no variant, and parts 1 and 2 leave their other kernels out.
 DZ_PARTS := 1 2
 HIP_OBJ  += $(OBJDIR)/hipdz_nh_kernels.o $(OBJDIR)/hipdz_nh_disney.o $(OBJDIR)/hipdz_nh_emitter_query.o \
             $(foreach k,$(DZ_PARTS),$(OBJDIR)/hipdz_nh_wavefront_p$(k).o)
-HIP_DEPS := $(wildcard $(PKG)/csrc/*.h) include/nori_hip.h
+HIP_DEPS := $(wildcard $(PKG)/csrc/*.h) $(PKG)/host/gpu_layout.h include/nori_hip.h
 # The wavefront kernels build without LLVM's machine-level LICM: it hoists loop invariants out of the traversal, bounce
 # and tail loops into registers for the loop's whole length, which then spill (wf_tail_rr at 4 waves/SIMD: 448 ->
 # 28 B/lane of scratch; wf_tail 256 -> 157 VGPRs; the persistent traversals 96 -> 88). C5 +3.6 %, other configs
@@ -53,8 +54,9 @@ RCPCHECK := tools/bin/rcp_exhaustive
 VALUBENCH := tools/bin/valu_issue
 
 MANUAL   := tests/c/bin/manual_scene
+LAYOUTCHECK := tests/c/bin/gpu_layout_check
 
-all: $(LIB) $(HOSTLIB) $(ORACLE) $(CLI) $(RCPCHECK) $(VALUBENCH) $(MANUAL)
+all: $(LIB) $(HOSTLIB) $(ORACLE) $(CLI) $(RCPCHECK) $(VALUBENCH) $(MANUAL) $(LAYOUTCHECK)
 
 # C test: a scene description filled field by field (no XML loader), rendered through the C-ABI and
 # compared with the oracle (run by tests/test_gpu_parity.py)
@@ -62,6 +64,12 @@ $(MANUAL): tests/c/manual_scene.c $(LIB) $(ORACLE) include/nori_hip.h oracle/nor
 	@mkdir -p tests/c/bin
 	$(CC) -std=c99 -O2 -Wall -Iinclude -Ioracle -o $@ $< -L$(LIBDIR) -lnori_hip -Loracle/_build -lnori_oracle \
 	    -lm -Wl,-rpath,'$$ORIGIN/../../../$(LIBDIR)' -Wl,-rpath,'$$ORIGIN/../../../oracle/_build'
+
+# C++ test: the host-side GPU layout code (host/gpu_layout.cpp) checked on the CPU, one scene per run (run by
+# tests/test_gpu_layout_host.py)
+$(LAYOUTCHECK): tests/c/gpu_layout_check.cpp $(HOSTLIB) $(PKG)/host/gpu_layout.h $(PKG)/csrc/nh_layout.h include/nori_hip.h
+	@mkdir -p tests/c/bin
+	$(CXX) $(HOST_FLAGS) -I$(PKG)/csrc -o $@ $< -L$(LIBDIR) -lnori_host -Wl,-rpath,'$$ORIGIN/../../../$(LIBDIR)'
 
 # exhaustive check of the fast reciprocal the traversal kernels use (run by the GPU tests)
 $(RCPCHECK): tools/rcp_exhaustive.hip $(HIP_DEPS)
@@ -73,7 +81,11 @@ $(VALUBENCH): tools/valu_issue.hip
 	@mkdir -p tools/bin
 	$(HIPCC) -std=c++17 -O3 --offload-arch=$(ARCH) -o $@ $<
 
-$(OBJDIR)/host_%.o: $(PKG)/host/%.cpp $(wildcard $(PKG)/host/*.h) include/nori_hip.h
+# the GPU layout code was part of the -O3 C-ABI unit before it moved to host/: at -O2 a 10M-triangle upload took 5 %
+# longer (profiles/api_split_bench.txt). Contraction stays off.
+$(OBJDIR)/host_gpu_layout.o: HOST_FLAGS += -O3
+
+$(OBJDIR)/host_%.o: $(PKG)/host/%.cpp $(wildcard $(PKG)/host/*.h) $(PKG)/csrc/nh_layout.h include/nori_hip.h
 	@mkdir -p $(OBJDIR)
 	$(CXX) $(HOST_FLAGS) -c $< -o $@
 

@@ -14,6 +14,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "nh_layout.h"
+
 namespace nhd {
 
 constexpr float kEps = 1e-4f;
@@ -22,9 +24,6 @@ constexpr float kInvPi = 0.31830988618379067154f;
 constexpr uint64_t kPcgMult = 0x5851f42d4c957f2dULL;
 
 #define NHD __device__ __forceinline__
-
-// lens-stream tables (DScene::lens_lo / lens_hi): rounds 256 h + l, h < kLensHi
-constexpr int kLensLo = 256, kLensHi = 65536;
 
 NHD float f_sin(float x) { return (float)sin((double)x); }
 NHD float f_cos(float x) { return (float)cos((double)x); }
@@ -209,7 +208,7 @@ struct alignas(16) DBsdf {
 // (alpha, int_ior) (disney_lo / disney_hi, disney_rec) -- DBsdf itself stays 48 bytes for the kernels that stage it to LDS. The ten clamped
 // parameters, the terms of eval that depend on them alone (ax, ay: disney.cpp:152-153; GTR1's a2 - 1 and
 // M_PI * log(a2) of the clearcoat lobe: :164, :311-313), and the terms that depend on the albedo (Cdlin, Cspec0,
-// Csheen: :132-137) for the constant albedo -- formed once at upload by the device functions below (nh_api.hip
+// Csheen: :132-137) for the constant albedo -- formed once at upload by the device functions below (nh_disney.hip
 // disney_fold_kernel), the same float operations in the same order as a textured albedo runs per hit.
 static_assert(sizeof(DBsdf) == 48 && offsetof(DBsdf, disney_lo) == 16 && offsetof(DBsdf, disney_hi) == 20 &&
                   offsetof(DBsdf, ext_ior) == 24, "DBsdf layout (staged to LDS as three float4)");
@@ -271,7 +270,7 @@ struct DScene {
     const float *area_cdf;
     // emitting meshes without vertex normals, per face: (p0, n.x) (p1, n.y) (p2, n.z) with the face normal
     // normalized(cross(p1 - p0, p2 - p0)) of Mesh::sampleSurface (mesh.cpp:64-69), computed once at upload by the
-    // same device arithmetic (nh_api.hip emit_face_kernel) instead of per light sample
+    // same device arithmetic (nh_upload.hip emit_face_kernel) instead of per light sample
     const float4 *emit_faces;
     // camera (perspective.cpp) and filter table (block.cpp)
     float s2c[16], c2w[16];
@@ -304,7 +303,7 @@ struct DScene {
     // BSDF albedo textures (DBsdf::tex) and the png texels they index
     const DTex *texs;
     const float4 *texels;
-    // 1: a light sample is always finite and never at a discrete-BSDF shading point (nh_api.hip, upload), so the
+    // 1: a light sample is always finite and never at a discrete-BSDF shading point (host/gpu_layout.cpp nee_finite, at upload), so the
     // wavefront shade skips the light sample of a discrete BSDF sample (it provably adds +-0)
     int nee_finite;
     // isolated dielectric spheres the BVH upload marked (nh_traverse.h trace_next; 0: no ray tries the shortcut)
@@ -636,7 +635,7 @@ NHD int emitter_pick(const DScene &S, float x) {
 }
 
 // The same search bracketed by a guide table (Chen & Asau's cutpoint method), bit-identical: guide[j] is the first
-// CDF index not below j / 2^bits (nh_api.hip env_guide), and the first index not below x is monotone in x, so for
+// CDF index not below j / 2^bits (nh_upload.hip env_guide), and the first index not below x is monotone in x, so for
 // j = floor(x * 2^bits) -- exact, a power-of-two scaling of x in [0, 1) -- it lies in [guide[j], guide[j + 1]]:
 // the binary search runs over that bracket (a few entries) instead of the whole CDF (21 dependent loads for
 // C5's 1500 x 750 envmap).

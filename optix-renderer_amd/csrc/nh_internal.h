@@ -1,4 +1,4 @@
-// Internal structures shared between the C-ABI layer (nh_api.hip) and the kernels.
+// Internal structures shared between the C-ABI layer (nh_api.hip, nh_upload.hip, nh_pipeline.hip) and the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -178,7 +178,7 @@ struct WfLaunch {
     // kernels (0 = traverse from HBM)
     int small_nodes, small_leaves, small_prims;
     int small_frames;  // 1: the fused kernels also stage the flat triangles' shading frames (Traversal::frames)
-    // The LDS image of a small scene, built once per upload (nh_api.hip build_small_image): float4 regions in this
+    // The LDS image of a small scene, built once per upload (nh_upload.hip build_small_image): float4 regions in this
     // order -- nodes, primitive records, leaf table, pair records, scene tables, flat-triangle frames -- which the
     // fused kernels copy as it stands (stage_small_scene). small_tab: float4 counts of the table regions (shapes,
     // bsdfs, emitters, the emitting meshes' area CDFs, emit_faces), all 0 when the tables are not staged (over

@@ -473,7 +473,7 @@ __global__ __launch_bounds__(BLOCK, MINW) void nh_path_kernel(const DScene *__re
 }
 
 // ---------------------------------------------------------------------------
-// host-side launchers (called from nh_api.hip)
+// host-side launchers (called from nh_api.hip and nh_pipeline.hip)
 // ---------------------------------------------------------------------------
 namespace nh {
 

@@ -1,0 +1,24 @@
+// GPU BVH / lens-table layout constants shared by the kernels (nh_traverse.h, nh_device.h) and the host code that
+// builds those arrays (host/gpu_layout.cpp). Plain C++: no HIP header, so the host library compiles it too.
+#pragma once
+
+namespace nhd {
+
+// lens-stream tables (DScene::lens_lo / lens_hi): rounds 256 h + l, h < kLensHi
+constexpr int kLensLo = 256, kLensHi = 65536;
+
+// primitive record type / leaf-end bits (word 2 .w of the record), and the BSDF type of the owning
+// shape in bits 2-3 (the material key of the sorted shade queues)
+constexpr int kPrimSphere = 1, kPrimLeafEnd = 2, kPrimMatShift = 2;
+// an isolated sphere (record 2 .w bit; record 1 .x holds the host's margin m): see nh_traverse.h trace_next
+constexpr int kPrimIsolated = 16;
+
+// float4s of one 4-wide node (nh_traverse.h Tracer4: 128 B, one cache line); an 8-wide node is two of them
+constexpr int kWideF4 = 8;
+// child ref of an unused wide-node slot
+constexpr int kWideEmpty = (int)0x80000000;
+
+// deepest per-lane LDS stack of the binary-tree kernels (DEPTH template)
+constexpr int kMaxStack = 128;
+
+}  // namespace nhd

@@ -414,7 +414,7 @@ __device__ __forceinline__ F3 emitter_sample(const DScene &S, const DEmitter &e,
 // k = round * W * H + lens_index[pixel] takes draws 2k and 2k + 1, which pcg32::advance reaches directly: every
 // ray's lens sample is independent of how the rays are distributed over threads, blocks and ranks. (With several
 // threads the reference's draws race, so only its single-thread order is reproducible: DESIGN.md §7.)
-// The state at draw 2k is one affine map of the default state, composed from three table entries (nh_api.hip
+// The state at draw 2k is one affine map of the default state, composed from three table entries (host/gpu_layout.cpp
 // lens_tables: pcg32::advance is x -> a x + c mod 2^64, and advances compose and commute): two 64-bit multiply-adds
 // instead of pcg_advance's O(log k) loop. Point2f(nextFloat(), nextFloat()) as g++ evaluates it (right to left,
 // S.lens_rtl): x = draw 2k + 1, y = draw 2k.

@@ -1,7 +1,7 @@
 // BVH traversal for gfx950: BVH::rayIntersect (src/utils/bvh.cpp:402-460) semantics on
 // a GPU node layout.
 //
-// Layout (HBM, built by nh_api.hip from the reference's node array):
+// Layout (HBM, built by host/gpu_layout.cpp from the reference's node array):
 //   inner node (64 B) = 4 x float4:
 //     n0 = (L.min.xyz, L.max.x)  n1 = (L.max.yz, R.min.xy)  n2 = (R.min.z, R.max.xyz)
 //     n3 = (int L.ref, int R.ref, 0, 0)   ref >= 0: inner node, ref < 0: leaf ~ref
@@ -235,7 +235,7 @@ struct Traversal {
     // Frame(normalized(cross(p1 - p0, p2 - p0))), mesh.cpp:180-190), 3 float4 (s, t, n) per record, computed at
     // staging by the same arithmetic; nullptr: hit_info computes it
     const float4 *frames;
-    // the first n_top wide nodes are the top of the tree (the nodes most rays visit, nh_api.hip numbers
+    // the first n_top wide nodes are the top of the tree (the nodes most rays visit, host/gpu_layout.cpp numbers
     // them first); the persistent traversal kernels read those from an LDS copy
     int n_top;
 };
@@ -244,11 +244,7 @@ struct Traversal {
 //         centre and radius), e1 = p1 - p0, e2 = p2 - p0 (triangles only)
 constexpr int kPairF4 = 6;
 
-// primitive record type / leaf-end bits (word 2 .w of the record), and the BSDF type of the owning
-// shape in bits 2-3 (the material key of the sorted shade queues)
-constexpr int kPrimSphere = 1, kPrimLeafEnd = 2, kPrimMatShift = 2;
-// an isolated sphere (record 2 .w bit; record 1 .x holds the host's margin m): see trace_next
-constexpr int kPrimIsolated = 16;
+// primitive record bits (word 2 .w of the record): kPrimSphere, kPrimLeafEnd, kPrimMatShift, kPrimIsolated (nh_layout.h)
 NHD bool prim_is_tri(float4 c) { return (__float_as_int(c.w) & kPrimSphere) == 0; }
 NHD int prim_material(float4 c) { return (__float_as_int(c.w) >> kPrimMatShift) & 3; }
 
@@ -726,7 +722,7 @@ struct Tracer {
 };
 
 // ---------------------------------------------------------------------------------------------
-// 4-wide traversal of the same tree. nh_api.hip collapses the reference's binary tree: a wide
+// 4-wide traversal of the same tree. host/gpu_layout.cpp collapses the reference's binary tree: a wide
 // node's children are binary descendants (an inner child is replaced by its two children, the
 // largest-area one first, until there are 4), in left-first DFS order, with the descendants'
 // own boxes -- no new boxes. Skipping the boxes of the collapsed intermediate nodes changes no
@@ -741,13 +737,12 @@ struct Tracer {
 //   [0..5] min.x[4], min.y[4], min.z[4], max.x[4], max.y[4], max.z[4] of the 4 child slots
 //   [6]    int4 child refs: >= 0 wide node, kWideEmpty unused slot, else leaf ~first primitive
 //   [7]    unused
-constexpr int kWideF4 = 8;
+// (kWideF4 and kWideEmpty: nh_layout.h)
 // work per Tracer4::step for a lane: up to this many wide nodes, then up to two primitives
 #ifndef NH_NODES_PER_STEP
 #define NH_NODES_PER_STEP 1
 #endif
 
-constexpr int kWideEmpty = (int)0x80000000;
 // the two primitive records of a step tested as a packed pair (tri_test_pair) or one after the other
 #ifndef NH_WIDE_PAIR
 #define NH_WIDE_PAIR 1
@@ -1030,7 +1025,7 @@ struct Tracer4 {
 };
 
 // ---------------------------------------------------------------------------------------------
-// 8-wide traversal of the same tree (A/B against the 4-wide one, NH_WIDE8): nh_api.hip collapses the binary tree
+// 8-wide traversal of the same tree (A/B against the 4-wide one, NH_WIDE8): host/gpu_layout.cpp collapses the binary tree
 // to 8 children per node by the same rule (the largest-area inner child replaced by its two children, slots in
 // left-first DFS order, the descendants' own boxes -- no new boxes; the argument of Tracer4 carries over). A node
 // is two 128-B lines, each laid out as a 4-wide node: children 0-3 in float4 [0..7], 4-7 in [8..15]. Both lines

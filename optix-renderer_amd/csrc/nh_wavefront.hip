@@ -50,7 +50,7 @@ namespace {
 //   bits 4-5    path_mats bounce counter
 // F_FIRST (bounce 0, paths straight from the camera) lives in registers only.
 enum : int { F_DISCRETE = 1, F_NEE = 2, F_ZERO_COL = 4, F_ZNAN = 8, F_FIRST = 64 };
-constexpr int kPidBits = 26;  // path id bits of ray_d.w (nh_api.hip caps a chunk at 2^26 paths)
+constexpr int kPidBits = 26;  // path id bits of ray_d.w (nh_pipeline.hip nh_render caps a chunk at 2^26 paths)
 
 // rank of this lane among the wave's lanes with pred set, offset by the wave's reservation in
 // *counter (an LDS counter here)
@@ -963,7 +963,7 @@ __global__ __launch_bounds__(256, NH_DZ_WAVES(SORT, NH_SHADE_WAVES)) void wf_sha
     const int base = blockIdx.x * 256;
     if (base >= qv.n) return;  // whole workgroup
     // gridDim.x is a multiple of kQueueShards, so shard s receives the chunks c = s (mod 8):
-    // at most seg_cap entries (nh_api.hip sizes seg_cap so)
+    // at most seg_cap entries (nh_pipeline.hip pool_start sizes seg_cap so)
     const int shard = blockIdx.x & (kQueueShards - 1);
     if (threadIdx.x < 2) s_n[threadIdx.x] = 0u;
     const WfBuf &B = L.st.buf[L.in_q];
@@ -1574,7 +1574,7 @@ __global__ __launch_bounds__(256) void wf_camera_rays(const DScene *__restrict__
     }
 }
 
-// the computed regions of a small scene's LDS image, once per upload (nh_api.hip build_small_image)
+// the computed regions of a small scene's LDS image, once per upload (nh_upload.hip build_small_image)
 __global__ __launch_bounds__(256) void small_image_kernel(const float4 *prims, int n, float4 *pairs, float4 *frames) {
     build_pairs_frames(prims, n, pairs, frames, (int)threadIdx.x, 256);
 }
@@ -1768,7 +1768,7 @@ static void launch_wf_tail_d(const DScene *S, const Traversal &tv, const WfLaunc
 #if !NH_WF_SHADING_ONLY
 void launch_wf_trace2(const DScene *S, const Traversal &tv, const WfLaunch &L, bool ordered, bool stats, int wide,
                       int bound, hipStream_t st) {
-    // the wide trees are walked near-first only (nh_api.hip uses them for ordered traversals)
+    // the wide trees are walked near-first only (nh_pipeline.hip pool_start uses them for ordered traversals)
     (void)ordered;
     const int want = std::max(1, (bound + 127) / 128);
     if (wide == 8) {

@@ -1,0 +1,62 @@
+// Host-side layout of what the traversal and camera kernels read: the GPU BVH (binary nodes, leaf table, primitive
+// records, wide collapse), the isolated-sphere marks, the block spiral, the lens-stream tables and the nee_finite
+// scene flag. Plain C++ (no HIP): part of both libraries, and checked on the CPU by tests/c/gpu_layout_check.cpp.
+// The record formats are described where the kernels read them (csrc/nh_traverse.h); the constants both sides share
+// are in csrc/nh_layout.h.
+#pragma once
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "nori_hip.h"
+
+namespace nh {
+
+// stand-ins for HIP's float4 / int2 / ulonglong2: the C-ABI layer uploads these arrays as they are
+struct f4 {
+    float x, y, z, w;
+};
+struct i2 {
+    int x, y;
+};
+struct u64x2 {
+    uint64_t x, y;
+};
+
+struct GpuBvh {
+    std::vector<f4> nodes;   // 4 per inner node, left-first DFS order
+    std::vector<i2> leaves;  // (start, count) into the primitive records
+    std::vector<f4> prims;   // 3 per primitive in leaf order, leaf-end bits set, plus one zero record past the end
+    std::vector<f4> wide;    // wide_w / 4 * kWideF4 per wide node, the top n_top numbered first
+    std::vector<uint32_t> shape_offset;  // first primitive id of each shape, and the total
+    int root_kind = 0;       // 0 empty, 1 inner root, 2 the root is a leaf
+    float root_min[3] = {0.f, 0.f, 0.f}, root_max[3] = {0.f, 0.f, 0.f};
+    uint32_t tree_depth = 0;  // deepest level of the binary tree (root = 0), measured
+    int depth_wide = 1;       // stack bound of the wide traversal: (wide_w - 1) deferred entries per wide level, + 1
+    int n_top = 0;
+    int iso_spheres = 0;
+};
+
+// The GPU BVH of `b` over the scene's shapes (V, F: the scene's vertex and face arrays; shape_mat_key: the
+// kPrimMatShift bits of each shape's records; shape_bsdf_real: its NH_BSDF_*). wide_w: 4 or 8 children per wide node;
+// top_k: wide nodes to number first. NH_OK, or an error code with its message in err.
+int build_gpu_bvh(const nh_bvh_desc &b, const std::vector<nh_shape> &shapes, const std::vector<float> &V,
+                  const std::vector<uint32_t> &F, const std::vector<int> &shape_mat_key,
+                  const std::vector<int> &shape_bsdf_real, int wide_w, int top_k, GpuBvh &out, std::string &err);
+
+// the two steps of the wide tree, as build_gpu_bvh runs them
+std::vector<f4> collapse_wide(const std::vector<f4> &nodes, const std::vector<i2> &leaves, int &depth_out, int W = 4);
+int number_top_first(std::vector<f4> &wide, const float root_min[3], const float root_max[3], int K, int W = 4);
+
+std::vector<int> spiral_rank(int w, int h, int bs, int &nbx, int &nby);
+std::vector<uint32_t> serial_ray_index(int w, int h, int bs);
+
+struct LensTables {
+    std::vector<u64x2> pix, lo;
+    std::vector<uint64_t> hi;
+};
+LensTables lens_tables(int w, int h);
+
+bool nee_finite(const nh_scene_desc *d);
+
+}  // namespace nh
