@@ -35,8 +35,11 @@ HIP_OBJ  := $(patsubst $(PKG)/csrc/%.hip,$(OBJDIR)/hip_%.o,$(HIP_SRC)) \
 # kernel. It also holds the spot / directional light branches (kExtLights). Scenes without a Disney BSDF or one of
 # those lights never launch these (nh_ctx.h NH_LAUNCH). Only what shades is built: parts 0 and 3 (traversal kernels) and
 # part 4 (the diffuse area-light instantiations) have no variant, and parts 1 and 2 leave their other kernels out.
+# nh_volume.hip (the volumetric path tracers and the medium query) is built this way only: one copy, with every BSDF
+# and emitter type.
 DZ_PARTS := 1 2
 HIP_OBJ  += $(OBJDIR)/hipdz_nh_kernels.o $(OBJDIR)/hipdz_nh_disney.o $(OBJDIR)/hipdz_nh_emitter_query.o \
+            $(OBJDIR)/hipdz_nh_volume.o \
             $(foreach k,$(DZ_PARTS),$(OBJDIR)/hipdz_nh_wavefront_p$(k).o)
 HIP_DEPS := $(wildcard $(PKG)/csrc/*.h) $(PKG)/host/gpu_layout.h include/nori_hip.h
 # The wavefront kernels build without LLVM's machine-level LICM: it hoists loop invariants out of the traversal, bounce

@@ -62,13 +62,17 @@ enum { NH_EMITTER_AREA = 0, NH_EMITTER_POINT = 1, NH_EMITTER_ENVMAP = 2, NH_EMIT
  * (normals.cpp: |shFrame.toWorld(direction)|, the envmap on a miss) */
 enum { NH_INTEGRATOR_PATH_MIS = 0, NH_INTEGRATOR_PATH_MATS = 1, NH_INTEGRATOR_DIRECT_EMS = 2,
        NH_INTEGRATOR_DIRECT_MATS = 3, NH_INTEGRATOR_DIRECT_MIS = 4, NH_INTEGRATOR_DIRECT = 5,
-       NH_INTEGRATOR_NORMALS = 6 };
+       NH_INTEGRATOR_NORMALS = 6,
+       /* the volumetric path tracers (path_vol_mats.cpp, path_vol_mis.cpp): the only integrators that render a scene
+          with a participating medium or a shape without a BSDF */
+       NH_INTEGRATOR_PATH_VOL_MATS = 7, NH_INTEGRATOR_PATH_VOL_MIS = 8 };
 
 /* One Nori Shape (src/shapes/mesh.cpp, src/shapes/sphere.cpp). Mesh data lives in
  * the scene-wide concatenated arrays at the given offsets. */
 typedef struct nh_shape {
     int32_t type;            /* NH_SHAPE_* */
-    int32_t bsdf;            /* index into nh_scene_desc.bsdfs (every shape has one; default diffuse 0.5) */
+    int32_t bsdf;            /* index into nh_scene_desc.bsdfs (default diffuse 0.5); -1 = none, legal only for a shape
+                                with a medium (nh_scene_desc.shape_medium; Shape::cloneAndInit, shape.cpp:33-35) */
     int32_t emitter;         /* index into nh_scene_desc.emitters, or -1 */
     uint32_t v_offset;       /* first vertex in V/N/UV/T/BT */
     uint32_t n_vertices;
@@ -161,6 +165,23 @@ typedef struct nh_emitter_ext {
     float pad;
 } nh_emitter_ext;
 
+/* One Nori Medium (src/media/{vacuum,homogmedium}.cpp, medium.cpp) with its phase function (src/bsdf/isophase.cpp,
+ * anisophase.cpp). nh_upload_scene rejects a type outside NH_MEDIUM_VACUUM..NH_MEDIUM_HOMOG or a phase outside
+ * NH_PHASE_ISO..NH_PHASE_HG with NH_ERR_INVALID. The coefficients are the derived ones, each an fp32 product in this
+ * order: sigma_x = sigma_x (normalized colour) * sigma_x_intensity, mu_a = density * sigma_a, mu_s = density * sigma_s,
+ * mu_t = mu_a + mu_s (defaults: sigma_a 0.5, sigma_s 0, intensities 1, density 1). */
+enum { NH_MEDIUM_VACUUM = 0, NH_MEDIUM_HOMOG = 1 };
+enum { NH_PHASE_ISO = 0, NH_PHASE_HG = 1 };
+typedef struct nh_medium {
+    int32_t type;            /* NH_MEDIUM_* */
+    float mu_a[3];           /* absorption coefficient */
+    float mu_s[3];           /* scattering coefficient */
+    float mu_t[3];           /* extinction coefficient */
+    float density;
+    int32_t phase;           /* NH_PHASE_* */
+    float g;                 /* NH_PHASE_HG: Henyey-Greenstein's g (anisophase.cpp) */
+} nh_medium;
+
 /* PerspectiveCamera after update() (src/cameras/perspective.cpp:48-96). Row-major 4x4. */
 typedef struct nh_camera {
     int32_t width, height;
@@ -250,6 +271,12 @@ typedef struct nh_scene_desc {
     /* Appended (clients that fill the fields above by name compile unchanged): n_emitters entries, or NULL when the
        scene has no spot / directional light */
     const nh_emitter_ext *emitter_ext;
+    /* Appended: participating media. A zero-filled tail means "no media". */
+    uint32_t n_media;
+    const nh_medium *media;
+    const uint32_t *shape_medium; /* n_shapes entries: 1 + index into media of the shape's <medium>, 0 = none; may be
+                                     NULL (no shape has a medium) */
+    uint32_t ambient_medium;      /* 1 + index into media of the scene's ambient <medium>, 0 = vacuum */
 } nh_scene_desc;
 
 /* ---- BVH in the reference's own layout (include/nori/bvh.h:127-165) ---- */
@@ -494,6 +521,17 @@ enum { NH_EMITTER_QUERY_SAMPLE = 0, NH_EMITTER_QUERY_EVAL = 1, NH_EMITTER_QUERY_
 #define NH_EMITTER_QUERY_IN_STRIDE 9
 int nh_emitter_query(nh_ctx *ctx, uint32_t emitter, int32_t mode, int32_t n, const float *ref, const float *sample,
                      float *out);
+/* Medium queries on the device, by the device functions the volumetric path kernel calls (nh_volume.hip): medium
+ * `medium` of the uploaded scene, n queries, one lane each.
+ *   NH_MEDIUM_QUERY_FREE_PATH      in: 2n floats (the two uniforms sampleFreePath may draw, in draw order).
+ *                                  out: 2n floats: t, and the number of draws it consumed (0, 1 or 2)
+ *   NH_MEDIUM_QUERY_TRANSMITTANCE  in: 6n floats (from, to). out: 3n floats
+ *   NH_MEDIUM_QUERY_PHASE_SAMPLE   in: 2n floats (the 2D sample). out: 4n floats: wo (local frame, wi = +z), pdf(wo)
+ *   NH_MEDIUM_QUERY_PHASE_PDF      in: 3n floats (wo). out: n floats
+ * Needs an uploaded scene (nh_upload_scene; no BVH). */
+enum { NH_MEDIUM_QUERY_FREE_PATH = 0, NH_MEDIUM_QUERY_TRANSMITTANCE = 1, NH_MEDIUM_QUERY_PHASE_SAMPLE = 2,
+       NH_MEDIUM_QUERY_PHASE_PDF = 3 };
+int nh_medium_query(nh_ctx *ctx, uint32_t medium, int32_t mode, int32_t n, const float *in, float *out);
 const char *nh_last_error(const nh_ctx *ctx);
 
 #ifdef __cplusplus

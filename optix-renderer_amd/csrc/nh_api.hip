@@ -237,6 +237,42 @@ int nh_emitter_query(nh_ctx *c, uint32_t emitter, int32_t mode, int32_t n, const
     return NH_OK;
 }
 
+int nh_medium_query(nh_ctx *c, uint32_t medium, int32_t mode, int32_t n, const float *in, float *out) {
+    if (!c) return NH_ERR_INVALID;
+    if (n < 0 || !in || !out) return fail(c, "nh_medium_query: null argument"), NH_ERR_INVALID;
+    if (mode < NH_MEDIUM_QUERY_FREE_PATH || mode > NH_MEDIUM_QUERY_PHASE_PDF)
+        return fail(c, "nh_medium_query: unknown mode"), NH_ERR_INVALID;
+    if (!c->has_scene) return fail(c, "nh_medium_query: no scene uploaded"), NH_ERR_STATE;
+    if (medium >= (uint32_t)c->S.n_media) return fail(c, "nh_medium_query: medium index out of range"), NH_ERR_INVALID;
+    if (n == 0) return NH_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc_ = pipeline_drain(c)) return rc_;
+    std::vector<void *> bufs;  // freed on every return
+    struct Free {
+        std::vector<void *> &v;
+        ~Free() { free_all(v); }
+    } guard{bufs};
+    // the scene record as nh_upload_scene left it (as nh_emitter_query: the medium functions read no BVH field)
+    const nhd::DScene *d_s = nullptr;
+    if (int rc = upload(c, bufs, &c->S, 1, &d_s)) return rc;
+    static const size_t kIn[4] = {2, 6, 2, 3}, kOut[4] = {2, 3, 4, 1};
+    const size_t sn = (size_t)n, in_stride = kIn[mode], out_stride = kOut[mode];
+    nh_disney::nh::MediumQuery q;
+    q.medium = (int)medium;
+    q.mode = mode;
+    q.n = n;
+    if (int rc = upload(c, bufs, in, in_stride * sn, &q.in)) return rc;
+    void *d_out = nullptr;
+    HIP_TRY(c, hipMalloc(&d_out, out_stride * sn * sizeof(float)));
+    bufs.push_back(d_out);
+    q.out = static_cast<float *>(d_out);
+    nh_disney::nh::launch_medium_query(d_s, q, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(out, d_out, out_stride * sn * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return NH_OK;
+}
+
 int nh_synchronize(nh_ctx *c) {
     if (!c) return NH_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));

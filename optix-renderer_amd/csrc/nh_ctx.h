@@ -151,6 +151,8 @@ struct nh_ctx {
     // path_mis, every BSDF diffuse with a constant albedo, every light an area light on a mesh with an emit_faces
     // record, no envmap, normal map or thin lens: the RR-ahead kernels' trait instantiations apply
     bool diffuse_area = false;
+    // a shape without a BSDF / a non-vacuum medium: only the volumetric integrators render the scene (nh_render)
+    bool bsdfless = false, has_media = false;
     // host copies of the scene tables and the emit_faces count, for the LDS image of a small scene (build_small_image)
     std::vector<nhd::DShape> h_shapes;
     std::vector<nhd::DBsdf> h_bsdfs;

@@ -249,6 +249,18 @@ struct alignas(16) DEmitterExt {
     float nx, ny, nz, pad;          // m_coord.n
 };
 static_assert(sizeof(DEmitter) == 32 && sizeof(DEmitterExt) == 64, "emitter records");
+// Medium (vacuum.cpp, homogmedium.cpp) with its phase function (isophase.cpp, anisophase.cpp): nh_medium's layout
+enum : int { MEDIUM_VACUUM = 0, MEDIUM_HOMOG = 1 };
+enum : int { PHASE_ISO = 0, PHASE_HG = 1 };
+struct alignas(16) DMedium {
+    int type;
+    float mu_a[3], mu_s[3], mu_t[3];
+    float density;
+    int phase;
+    float g;
+    int pad[3];
+};
+static_assert(sizeof(DMedium) == 64, "medium record");
 
 struct DScene {
     // BVH: 4 float4 per inner node, 3 float4 per primitive in leaf order
@@ -310,6 +322,13 @@ struct DScene {
     int iso_spheres;
     // spot / directional lights: n_emitters records indexed by DEmitter::shape (nullptr: the scene has neither)
     const DEmitterExt *emitter_ext;
+    // participating media (read by the volumetric path kernel alone, nh_volume.hip): the medium table, the per-shape
+    // side table (1 + medium index, 0 = none; DShape is full at 64 B) and the ambient medium (1 + index, 0 = vacuum).
+    // nullptr / 0 for a scene without media.
+    const DMedium *media;
+    const int *shape_medium;
+    int ambient_medium;
+    int n_media;
 };
 
 NHD F3 ldv(const float *a, uint32_t i) { return f3(a[3 * i], a[3 * i + 1], a[3 * i + 2]); }

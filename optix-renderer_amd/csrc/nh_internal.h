@@ -103,6 +103,18 @@ constexpr int kStatBounceClk = 40;
 __device__ __forceinline__ unsigned long long *stat_shard(unsigned long long *c) {
     return c + (blockIdx.x & (kStatShards - 1)) * kStatStride;
 }
+// a kernel's closest / any-hit work into counters[0-3] (the megakernels: nh_kernels.hip, nh_volume.hip)
+__device__ __forceinline__ void flush_stats(const nhd::TravStats &st, uint32_t queries, unsigned long long *counters) {
+    // one atomic per wave: reduce over the 64 lanes first
+    unsigned long long v[4] = {queries, st.nodes, st.boxes, st.prims};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        unsigned long long x = v[i];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+        if ((threadIdx.x & 63) == 0) atomicAdd(&counters[i], x);
+    }
+}
 
 namespace nh {
 void launch_trace(const nhd::DScene *S, const nhd::Traversal &tv, const RayBatch &rb, const HitBatch &hb, int n,
@@ -282,5 +294,18 @@ struct EmitterQuery {
     float *out;
 };
 void launch_emitter_query(const nhd::DScene *S, const EmitterQuery &q, hipStream_t st);
+// nh_volume.hip. The volumetric path tracers (path_vol_mats / path_vol_mis: S->integrator 7 / 8), one thread per
+// (pixel, round) like launch_path, writing the same sample records; built once, with every BSDF and emitter type.
+// The closest hits are walked nearer child first whatever the request's traversal (every order returns the same hit).
+void launch_vol_path(const nhd::DScene *S, const nhd::Traversal &tv, const PathLaunch &L, bool mis, bool stats, int depth,
+                     hipStream_t st);
+// nh_medium_query's kernel: medium_free_path (mode 0), medium_transmittance (1), phase_sample + phase_pdf (2) or
+// phase_pdf (3) of S.media[medium], n queries. in / out: 2 / 2, 6 / 3, 2 / 4, 3 / 1 floats per query
+struct MediumQuery {
+    int medium, mode, n;
+    const float *in;
+    float *out;
+};
+void launch_medium_query(const nhd::DScene *S, const MediumQuery &q, hipStream_t st);
 }  // namespace nh
 }  // namespace nh_disney

@@ -189,18 +189,6 @@ __device__ F3 li_path_mats(const DScene &S, const Traversal &tv, Rng &rng, F3 o,
     return li;
 }
 
-__device__ __forceinline__ void flush_stats(const TravStats &st, uint32_t queries, unsigned long long *counters) {
-    // one atomic per wave: reduce over the 64 lanes first
-    unsigned long long v[4] = {queries, st.nodes, st.boxes, st.prims};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        unsigned long long x = v[i];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-        if ((threadIdx.x & 63) == 0) atomicAdd(&counters[i], x);
-    }
-}
-
 }  // namespace
 
 template <int BLOCK, int DEPTH, bool ORDERED, bool ANY, bool STATS>

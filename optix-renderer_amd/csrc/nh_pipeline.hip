@@ -788,8 +788,17 @@ int nh_render(nh_ctx *c, const nh_render_req *q) {
     if ((c->integrator == NH_INTEGRATOR_PATH_MIS || c->integrator == NH_INTEGRATOR_DIRECT_MIS) && c->n_emitters == 0)
         return fail(c, "No Emitter in scene!"), NH_ERR_INVALID;
     if (q->mode != NH_MODE_MEGAKERNEL && q->mode != NH_MODE_WAVEFRONT) return fail(c, "unknown render mode"), NH_ERR_INVALID;
+    const bool volumetric = c->integrator == NH_INTEGRATOR_PATH_VOL_MATS || c->integrator == NH_INTEGRATOR_PATH_VOL_MIS;
+    // the surface integrators dereference every hit shape's BSDF and know no medium (the reference would crash, or
+    // silently drop the media): their kernels keep the "every shape has a BSDF" assumption
+    if (!volumetric && (c->bsdfless || c->has_media))
+        return fail(c, "the scene has a participating medium or a shape without a BSDF: only the path_vol_mats and "
+                       "path_vol_mis integrators render it"), NH_ERR_UNSUPPORTED;
+    if (c->integrator == NH_INTEGRATOR_PATH_VOL_MIS && c->n_emitters == 0)  // sampleEmitter would pick from an empty list
+        return fail(c, "No Emitter in scene!"), NH_ERR_INVALID;
     // the single-bounce direct integrators always run as the megakernel: one closest hit, the light
-    // sample(s) and at most one BSDF ray per path leave no bounce loop for path queues to balance
+    // sample(s) and at most one BSDF ray per path leave no bounce loop for path queues to balance. The volumetric
+    // path tracers have no wavefront version yet: a wavefront request runs their megakernel (nh_volume.hip)
     const bool wavefront = q->mode == NH_MODE_WAVEFRONT && c->integrator <= NH_INTEGRATOR_PATH_MATS;
     if (q->traversal < NH_TRAVERSAL_REFERENCE || q->traversal > NH_TRAVERSAL_WIDE)
         return fail(c, "unknown traversal"), NH_ERR_INVALID;
@@ -896,7 +905,11 @@ int nh_render(nh_ctx *c, const nh_render_req *q) {
             HIP_TRY(c, hipEventCreate(&ev.b));
             HIP_TRY(c, hipEventCreate(&ev.d));
             HIP_TRY(c, hipEventRecord(ev.a, c->stream));
-            NH_LAUNCH(c, launch_path)(c->d_scene, c->tv, L, q->traversal != NH_TRAVERSAL_REFERENCE, q->collect_stats != 0,
+            if (volumetric)
+                nh_disney::nh::launch_vol_path(c->d_scene, c->tv, L, c->integrator == NH_INTEGRATOR_PATH_VOL_MIS,
+                                               q->collect_stats != 0, c->depth, c->stream);
+            else
+                NH_LAUNCH(c, launch_path)(c->d_scene, c->tv, L, q->traversal != NH_TRAVERSAL_REFERENCE, q->collect_stats != 0,
                             c->depth, c->integrator == NH_INTEGRATOR_PATH_MIS && !c->normal_mapped, c->stream);
             HIP_TRY(c, hipGetLastError());
             HIP_TRY(c, hipEventRecord(ev.b, c->stream));

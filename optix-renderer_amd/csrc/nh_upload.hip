@@ -90,7 +90,16 @@ int nh_upload_scene(nh_ctx *c, const nh_scene_desc *d) {
     std::vector<DShape> ds(d->n_shapes);
     for (uint32_t i = 0; i < d->n_shapes; ++i) {
         const nh_shape &s = d->shapes[i];
-        if (s.bsdf < 0 || (uint32_t)s.bsdf >= d->n_bsdfs) return fail(c, "shape without a valid BSDF"), NH_ERR_INVALID;
+        // a shape with a medium may have no BSDF (bsdf = -1; Shape::cloneAndInit, shape.cpp:33-35): only the volumetric
+        // integrators render such a scene (nh_render)
+        const uint32_t sm = d->shape_medium ? d->shape_medium[i] : 0u;
+        if (sm > d->n_media || (sm && !d->media)) return fail(c, "shape medium index out of range"), NH_ERR_INVALID;
+        if (s.bsdf == -1 && !sm) return fail(c, "shape without a BSDF and without a medium"), NH_ERR_INVALID;
+        if (s.bsdf < -1 || (s.bsdf >= 0 && (uint32_t)s.bsdf >= d->n_bsdfs))
+            return fail(c, "shape without a valid BSDF"), NH_ERR_INVALID;
+        const bool bsdf_tex = s.bsdf >= 0 &&
+                              (d->bsdfs[s.bsdf].type == NH_BSDF_DIFFUSE || d->bsdfs[s.bsdf].type == NH_BSDF_DISNEY) &&
+                              d->bsdfs[s.bsdf].albedo_texture != 0;
         DShape &o = ds[i];
         std::memset(&o, 0, sizeof(o));
         o.type = s.type;
@@ -108,10 +117,7 @@ int nh_upload_scene(nh_ctx *c, const nh_scene_desc *d) {
         if (s.normal_map > d->n_textures || (s.normal_map && !d->textures))
             return fail(c, "shape normal map index out of range"), NH_ERR_INVALID;
         // bit 0: uv read (textured albedo or normal map); bits 1+: 1 + the normal map's texture index
-        o.tex_uv = ((int)s.normal_map << 1) |
-                   (((d->bsdfs[s.bsdf].type == NH_BSDF_DIFFUSE || d->bsdfs[s.bsdf].type == NH_BSDF_DISNEY) &&
-                     d->bsdfs[s.bsdf].albedo_texture != 0) || s.normal_map
-                        ? 1 : 0);
+        o.tex_uv = ((int)s.normal_map << 1) | (bsdf_tex || s.normal_map ? 1 : 0);
         o.ef_off = -1;
     }
     // emitting meshes without vertex normals: one emit_faces record per face (vertex index triples here)
@@ -206,9 +212,32 @@ int nh_upload_scene(nh_ctx *c, const nh_scene_desc *d) {
             o.shape = (int)i;  // the light's DScene::emitter_ext entry
         }
     }
+    // participating media: the table as it stands (nh_medium is DMedium's leading part) and the per-shape side table
+    std::vector<nhd::DMedium> dm(d->n_media);
+    std::vector<int> shape_medium;
+    if (d->n_media && !d->media) return fail(c, "media table missing"), NH_ERR_INVALID;
+    if (d->ambient_medium > d->n_media) return fail(c, "ambient medium index out of range"), NH_ERR_INVALID;
+    for (uint32_t i = 0; i < d->n_media; ++i) {
+        const nh_medium &m = d->media[i];
+        if (m.type < NH_MEDIUM_VACUUM || m.type > NH_MEDIUM_HOMOG) return fail(c, "unknown medium type"), NH_ERR_INVALID;
+        if (m.phase < NH_PHASE_ISO || m.phase > NH_PHASE_HG) return fail(c, "unknown phase function type"), NH_ERR_INVALID;
+        static_assert(sizeof(nh_medium) <= sizeof(nhd::DMedium), "nh_medium is DMedium's leading part");
+        std::memset(&dm[i], 0, sizeof(dm[i]));
+        std::memcpy(&dm[i], &m, sizeof(m));
+    }
+    c->bsdfless = false;
+    c->has_media = false;
+    for (uint32_t i = 0; i < d->n_shapes; ++i) c->bsdfless = c->bsdfless || d->shapes[i].bsdf < 0;
+    for (uint32_t i = 0; i < d->n_media; ++i) c->has_media = c->has_media || d->media[i].type != NH_MEDIUM_VACUUM;
+    if (d->n_media && d->shape_medium) shape_medium.assign(d->shape_medium, d->shape_medium + d->n_shapes);
     nhd::DScene &S = c->S;
     std::memset(&S, 0, sizeof(S));
     int rc;
+    if (!dm.empty() && (rc = upload(c, c->scene_bufs, dm.data(), dm.size(), &S.media))) return rc;
+    if (!shape_medium.empty() && (rc = upload(c, c->scene_bufs, shape_medium.data(), shape_medium.size(), &S.shape_medium)))
+        return rc;
+    S.ambient_medium = (int)d->ambient_medium;
+    S.n_media = (int)d->n_media;
     const size_t nv = d->n_vertices;
     if ((rc = upload(c, c->scene_bufs, ds.data(), ds.size(), &S.shapes))) return rc;
     if ((rc = upload(c, c->scene_bufs, db.data(), db.size(), &S.bsdfs))) return rc;
@@ -290,7 +319,7 @@ int nh_upload_scene(nh_ctx *c, const nh_scene_desc *d) {
     }
     S.n_emitters = (int)d->n_emitters;
     S.nee_finite = nh::nee_finite(d) ? 1 : 0;
-    if (d->integrator < NH_INTEGRATOR_PATH_MIS || d->integrator > NH_INTEGRATOR_NORMALS)
+    if (d->integrator < NH_INTEGRATOR_PATH_MIS || d->integrator > NH_INTEGRATOR_PATH_VOL_MIS)
         return fail(c, "unknown integrator"), NH_ERR_INVALID;
     S.integrator = d->integrator;
     for (int i = 0; i < 3; ++i) S.ndir[i] = d->normals_direction[i];
@@ -343,7 +372,8 @@ int nh_upload_scene(nh_ctx *c, const nh_scene_desc *d) {
     c->shape_bsdf_real.clear();
     unsigned types = 0;
     for (uint32_t i = 0; i < d->n_shapes; ++i) {
-        const int t = d->bsdfs[d->shapes[i].bsdf].type;  // 0..4 (checked above)
+        // 0..4 (checked above); a shape without a BSDF ranks with the diffuse ones (the key only orders shading work)
+        const int t = d->shapes[i].bsdf < 0 ? NH_BSDF_DIFFUSE : d->bsdfs[d->shapes[i].bsdf].type;
         c->shape_bsdf_real.push_back(t);
         types |= 1u << t;
     }

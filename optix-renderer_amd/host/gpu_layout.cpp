@@ -180,6 +180,7 @@ bool nee_finite(const nh_scene_desc *d) {
         if (si.emitter < 0) continue;
         for (uint32_t j = 0; j < d->n_shapes; ++j) {
             const nh_shape &sj = d->shapes[j];
+            if (sj.bsdf < 0) continue;  // (no BSDF: a medium boundary)
             const int t = d->bsdfs[sj.bsdf].type;
             if (t != NH_BSDF_MIRROR && t != NH_BSDF_DIELECTRIC) continue;
             Box bj;

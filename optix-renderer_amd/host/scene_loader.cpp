@@ -232,6 +232,10 @@ struct SceneData {
     std::vector<nh_texture> textures;  // BSDF albedo textures (nh_bsdf.albedo_texture = index + 1)
     std::vector<float> texels;         // RGBA texels of the png textures
     nh_denoiser denoiser{};  // type NH_DENOISER_NONE unless the scene has a <denoiser>
+    // participating media: shape_medium is empty, or one entry per shape (1 + medium index, 0 = none)
+    std::vector<nh_medium> media;
+    std::vector<uint32_t> shape_medium;
+    uint32_t ambient_medium = 0;  // 1 + medium index, 0 = the default vacuum
     // camera parameters kept for re-projection on resize
     float fov = 30.f, near_clip = 1e-4f, far_clip = 1e4f, focal = 10.f, fstop = 0.f, lens = 0.f;
     // Independent::next2D's argument order as g++ compiles it (nh_camera.lens_draw_order)
@@ -915,8 +919,57 @@ void set_emitter_ext(SceneData &sd, const nh_emitter_ext &x) {
     sd.emitter_ext.back() = x;
 }
 
+// Medium (medium.cpp:10-17, :49-69) with HomogeneousMedium's density (homogmedium.cpp:16-19) and its phase function
+// (isophase.cpp, anisophase.cpp:16-19; isophase when it has none, medium.cpp:21-23). The derived coefficients as
+// Medium::updateDerivedProperties (medium.cpp:112-117) and HomogeneousMedium::updateDerivedProperties
+// (homogmedium.cpp:48-54) form them, each one fp32 product or sum: sigma = normalized * intensity, mu = density * sigma,
+// mu_t = mu_a + mu_s.
+nh_medium make_medium(const Obj &o) {
+    nh_medium m{};
+    if (o.type == "vacuum") m.type = NH_MEDIUM_VACUUM;
+    else if (o.type == "homog") m.type = NH_MEDIUM_HOMOG;
+    else if (o.type == "heterog")
+        throw SceneError("medium \"heterog\" (heterogeneous NanoVDB media) is not supported by the HIP path");
+    else throw SceneError("medium \"" + o.type + "\" is not supported by the HIP path");
+    const V3 sa = o.props.get_color("sigma_a", v3(0.5f, 0.5f, 0.5f)), ss = o.props.get_color("sigma_s", v3(0, 0, 0));
+    const float ia = o.props.get_float("sigma_a_intensity", 1.f), is = o.props.get_float("sigma_s_intensity", 1.f);
+    m.density = m.type == NH_MEDIUM_HOMOG ? o.props.get_float("density", 1.f) : 1.f;
+    const float sigma_a[3] = {sa.x * ia, sa.y * ia, sa.z * ia}, sigma_s[3] = {ss.x * is, ss.y * is, ss.z * is};
+    for (int k = 0; k < 3; ++k) {
+        m.mu_a[k] = m.density * sigma_a[k];
+        m.mu_s[k] = m.density * sigma_s[k];
+        m.mu_t[k] = m.mu_a[k] + m.mu_s[k];
+    }
+    m.phase = NH_PHASE_ISO;
+    bool have_phase = false;
+    for (auto &ch : o.children) {
+        if (ch->tag == "phase") {
+            if (have_phase) throw SceneError("Medium: tried to register multiple PhaseFunction instances!");
+            have_phase = true;
+            if (ch->type == "isophase") {
+                m.phase = NH_PHASE_ISO;
+            } else if (ch->type == "anisophase") {
+                m.phase = NH_PHASE_HG;
+                m.g = ch->props.get_float("g", 0.f);
+            } else if (ch->type == "schlick") {
+                // Warp::squareToSchlick (warp.cpp:207-233) takes cosTheta outside [-1, 1] for ordinary k: the reference
+                // renders NaN with it, so there is nothing to reproduce
+                throw SceneError("phase function \"schlick\" is not supported (the reference's warp leaves [-1, 1] "
+                                 "and renders NaN)");
+            } else {
+                throw SceneError("phase function \"" + ch->type + "\" is not supported");
+            }
+        } else if (ch->tag == "emitter") {
+            throw SceneError("a medium's <emitter> (volume light) is not supported by the HIP path");
+        } else {
+            throw SceneError("Medium::addChild(<" + ch->tag + ">) is not supported!");
+        }
+    }
+    return m;
+}
+
 void build_scene(const Obj &scene, const std::string &base_dir, SceneData &sd) {
-    bool have_camera = false, have_integrator = false, have_sampler = false;
+    bool have_camera = false, have_integrator = false, have_sampler = false, have_ambient = false;
     set_filter(sd.filter, 0, 2.0f, 0.5f, 1.0f / 3.0f, 1.0f / 3.0f);
     for (auto &chp : scene.children) {
         const Obj &ch = *chp;
@@ -929,6 +982,8 @@ void build_scene(const Obj &scene, const std::string &base_dir, SceneData &sd) {
             else if (ch.type == "direct_mats") sd.integrator = NH_INTEGRATOR_DIRECT_MATS;
             else if (ch.type == "direct_mis") sd.integrator = NH_INTEGRATOR_DIRECT_MIS;
             else if (ch.type == "direct") sd.integrator = NH_INTEGRATOR_DIRECT;
+            else if (ch.type == "path_vol_mats") sd.integrator = NH_INTEGRATOR_PATH_VOL_MATS;
+            else if (ch.type == "path_vol_mis") sd.integrator = NH_INTEGRATOR_PATH_VOL_MIS;
             else if (ch.type == "normals") {  // NormalIntegrator (normals.cpp:10-12)
                 sd.integrator = NH_INTEGRATOR_NORMALS;
                 const V3 dir = ch.props.get_point("direction", v3(0, 0, 1));
@@ -972,6 +1027,7 @@ void build_scene(const Obj &scene, const std::string &base_dir, SceneData &sd) {
             nh_shape sh{};
             sh.emitter = -1;
             int bsdf = -1, emitter = -1;
+            uint32_t medium = 0;
             nh_emitter em{};
             for (auto &sc : ch.children) {
                 if (sc->tag == "bsdf") {
@@ -986,8 +1042,10 @@ void build_scene(const Obj &scene, const std::string &base_dir, SceneData &sd) {
                     em.radiance[0] = r.x; em.radiance[1] = r.y; em.radiance[2] = r.z;
                     em.light_prob = sc->props.get_float("lightWeight", 1.f);
                     emitter = 1;
-                } else if (sc->tag == "medium") {
-                    throw SceneError("participating media are out of scope for path_mis");
+                } else if (sc->tag == "medium") {  // Shape::addChild EMedium (shape.cpp:132-136)
+                    if (medium) throw SceneError("Shape: tried to register multiple Medium instances.");
+                    sd.media.push_back(make_medium(*sc));
+                    medium = (uint32_t)sd.media.size();
                 } else if (sc->tag == "texture") {  // Shape::addChild ETexture (shape.cpp:138-147)
                     const std::string nm = sc->props.get_string("name", "");
                     if (nm != "normal") throw SceneError("Shape does not have a texture with name: " + nm);
@@ -998,7 +1056,7 @@ void build_scene(const Obj &scene, const std::string &base_dir, SceneData &sd) {
                     throw SceneError("shape child <" + sc->tag + "> is not supported");
                 }
             }
-            if (bsdf < 0) {  // Shape::cloneAndInit default diffuse
+            if (bsdf < 0 && !medium) {  // Shape::cloneAndInit default diffuse: only without a medium (shape.cpp:33-35)
                 sd.bsdfs.push_back(default_diffuse());
                 bsdf = (int)sd.bsdfs.size() - 1;
             }
@@ -1026,6 +1084,7 @@ void build_scene(const Obj &scene, const std::string &base_dir, SceneData &sd) {
                 sh.emitter = (int32_t)sd.emitters.size() - 1;
             }
             sd.shapes.push_back(sh);
+            sd.shape_medium.push_back(medium);
         } else if (ch.tag == "emitter") {
             nh_emitter em{};
             em.shape = -1;
@@ -1094,8 +1153,11 @@ void build_scene(const Obj &scene, const std::string &base_dir, SceneData &sd) {
             sd.denoiser.amount = clampi(ch.props.get_int("amount", 1), 1, 10);
         } else if (ch.tag == "renderer") {
             // OptixRenderer settings object (OptixRenderer.h:17-36): no effect on the path_mis hot path
-        } else if (ch.tag == "medium") {
-            if (ch.type != "vacuum") throw SceneError("participating media are out of scope for path_mis");
+        } else if (ch.tag == "medium") {  // Scene::addChild EMedium (scene.cpp:248-252)
+            if (have_ambient) throw SceneError("There can only be one ambient medium per scene.");
+            have_ambient = true;
+            sd.media.push_back(make_medium(ch));
+            sd.ambient_medium = (uint32_t)sd.media.size();
         } else {
             throw SceneError("Scene::addChild(<" + ch.tag + ">) is not supported");
         }
@@ -1166,6 +1228,10 @@ void fill_desc(const SceneData &sd, nh_scene_desc *d) {
     d->emitters = sd.emitters.data();
     d->emitter_cdf = sd.emitter_cdf.data();
     d->emitter_ext = sd.emitter_ext.empty() ? nullptr : sd.emitter_ext.data();
+    d->n_media = (uint32_t)sd.media.size();
+    d->media = sd.media.empty() ? nullptr : sd.media.data();
+    d->shape_medium = sd.media.empty() ? nullptr : sd.shape_medium.data();
+    d->ambient_medium = sd.ambient_medium;
     d->envmap = sd.envmap;
     d->denoiser = sd.denoiser;
     d->n_vertices = (uint32_t)(sd.V.size() / 3);
@@ -1287,7 +1353,7 @@ int nh_texture_decode(const uint8_t *rgba8, uint64_t n, int32_t srgb, float *out
 }
 
 int nh_scene_set_integrator(nh_scene *scene, int32_t integrator) {
-    if (!scene || integrator < NH_INTEGRATOR_PATH_MIS || integrator > NH_INTEGRATOR_NORMALS) {
+    if (!scene || integrator < NH_INTEGRATOR_PATH_MIS || integrator > NH_INTEGRATOR_PATH_VOL_MIS) {
         nh::set_host_error("invalid integrator");
         return NH_ERR_INVALID;
     }

@@ -39,6 +39,11 @@ EMITTER_QUERY_SAMPLE_STRIDE, EMITTER_QUERY_IN_STRIDE = 16, 9
 INTEGRATOR_PATH_MIS, INTEGRATOR_PATH_MATS, INTEGRATOR_DIRECT_EMS, INTEGRATOR_DIRECT_MATS, INTEGRATOR_DIRECT_MIS = 0, 1, 2, 3, 4
 INTEGRATOR_DIRECT = 5  # the point-light `direct` integrator of scenes/pa1 (direct.cpp)
 INTEGRATOR_NORMALS = 6  # the `normals` integrator of the normal-map scenes (normals.cpp)
+# the volumetric path tracers (path_vol_mats.cpp, path_vol_mis.cpp): the integrators that render participating media
+INTEGRATOR_PATH_VOL_MATS, INTEGRATOR_PATH_VOL_MIS = 7, 8
+MEDIUM_VACUUM, MEDIUM_HOMOG = 0, 1  # vacuum.cpp, homogmedium.cpp
+PHASE_ISO, PHASE_HG = 0, 1  # isophase.cpp, anisophase.cpp (Henyey-Greenstein)
+MEDIUM_QUERY_FREE_PATH, MEDIUM_QUERY_TRANSMITTANCE, MEDIUM_QUERY_PHASE_SAMPLE, MEDIUM_QUERY_PHASE_PDF = 0, 1, 2, 3
 MODE_MEGAKERNEL, MODE_WAVEFRONT = 0, 1
 SMALL_TABLES_BYTES = 4096  # NH_SMALL_TABLES_BYTES: LDS budget of the scene tables of the diffuse area-light kernels
 TRAVERSAL_REFERENCE, TRAVERSAL_ORDERED, TRAVERSAL_WIDE = 0, 1, 2
@@ -90,6 +95,11 @@ class nh_emitter_ext(C.Structure):
                 ("frame_t", _f * 3), ("cos_theta_max", _f), ("frame_n", _f * 3), ("pad", _f)]
 
 
+class nh_medium(C.Structure):
+    _fields_ = [("type", _i32), ("mu_a", _f * 3), ("mu_s", _f * 3), ("mu_t", _f * 3), ("density", _f),
+                ("phase", _i32), ("g", _f)]
+
+
 class nh_camera(C.Structure):
     _fields_ = [("width", _i32), ("height", _i32), ("sample_to_camera", _f * 16), ("camera_to_world", _f * 16),
                 ("inv_output_size", _f * 2), ("near_clip", _f), ("far_clip", _f), ("lens_radius", _f),
@@ -135,7 +145,9 @@ class nh_scene_desc(C.Structure):
                 ("UV", _fp), ("T", _fp), ("BT", _fp), ("n_faces", _u32), ("F", _u32p), ("n_area_cdf", _u32),
                 ("area_cdf", _fp), ("env", nh_envmap), ("denoiser", nh_denoiser), ("n_textures", _u32),
                 ("textures", C.POINTER(nh_texture)), ("n_texels", C.c_uint64), ("texels", _fp),
-                ("normals_direction", _f * 3), ("emitter_ext", C.POINTER(nh_emitter_ext))]
+                ("normals_direction", _f * 3), ("emitter_ext", C.POINTER(nh_emitter_ext)),
+                ("n_media", _u32), ("media", C.POINTER(nh_medium)), ("shape_medium", _u32p),
+                ("ambient_medium", _u32)]
 
 
 class nh_bvh_node(C.Structure):
@@ -236,6 +248,7 @@ _sig("nh_denoise", _i32, _vp, C.POINTER(nh_denoiser))
 _sig("nh_denoise_image", _i32, _vp, _fp, _i32, _i32, _i32, C.POINTER(nh_denoiser))
 _sig("nh_bsdf_query", _i32, _vp, C.POINTER(nh_bsdf), _fp, _i32, _i32, _fp, _fp, _fp, _fp, _fp, _fp, C.POINTER(_i32))
 _sig("nh_emitter_query", _i32, _vp, _u32, _i32, _i32, _fp, _fp, _fp)
+_sig("nh_medium_query", _i32, _vp, _u32, _i32, _i32, _fp, _fp)
 _sig("nh_last_error", C.c_char_p, _vp)
 
 lib = _lib
@@ -341,6 +354,23 @@ class Scene:
         if idx == 0:
             raise NoriError(f"add_texture: {_lib.nh_host_last_error().decode()}")
         return idx
+
+    def media(self) -> list:
+        """The scene's media as dicts (type, mu_a, mu_s, mu_t, density, phase, g), in nh_scene_desc.media order."""
+        d = self.desc
+        return [{"type": m.type, "mu_a": np.array(m.mu_a[:], np.float32), "mu_s": np.array(m.mu_s[:], np.float32),
+                 "mu_t": np.array(m.mu_t[:], np.float32), "density": np.float32(m.density), "phase": m.phase,
+                 "g": np.float32(m.g)} for m in (d.media[i] for i in range(d.n_media))]
+
+    def shape_media(self) -> list:
+        """Per shape: the index of its medium in media(), or -1 (nh_scene_desc.shape_medium, minus one)."""
+        d = self.desc
+        return [int(d.shape_medium[i]) - 1 if d.shape_medium else -1 for i in range(d.n_shapes)]
+
+    @property
+    def ambient_medium(self) -> int:
+        """The index of the scene's ambient medium in media(), or -1 for the default vacuum."""
+        return int(self.desc.ambient_medium) - 1
 
     def set_lens_draw_order(self, order: int):
         """LENS_DRAWS_RTL (default, g++'s evaluation of Point2f(nextFloat(), nextFloat())) or LENS_DRAWS_LTR."""
@@ -568,6 +598,18 @@ class Context:
         if mode in (None, EMITTER_QUERY_PDF):
             out["pdf"] = call(EMITTER_QUERY_PDF, inp, np.zeros(m, np.float32))
         return out
+
+    def medium_query(self, medium: int, mode: int, inp: np.ndarray) -> np.ndarray:
+        """nh_medium_query: queries of medium `medium` of the uploaded scene by the volumetric kernel's own device
+        functions. MEDIUM_QUERY_FREE_PATH: inp (m, 2) uniforms -> (m, 2): t and the draws consumed;
+        MEDIUM_QUERY_TRANSMITTANCE: inp (m, 6) from, to -> (m, 3); MEDIUM_QUERY_PHASE_SAMPLE: inp (m, 2) -> (m, 4): wo
+        and its pdf; MEDIUM_QUERY_PHASE_PDF: inp (m, 3) wo -> (m,)."""
+        n_in, n_out = {MEDIUM_QUERY_FREE_PATH: (2, 2), MEDIUM_QUERY_TRANSMITTANCE: (6, 3),
+                       MEDIUM_QUERY_PHASE_SAMPLE: (2, 4), MEDIUM_QUERY_PHASE_PDF: (3, 1)}[mode]
+        inp = np.ascontiguousarray(inp, dtype=np.float32).reshape(-1, n_in)
+        out = np.zeros((len(inp), n_out), np.float32)
+        self._check(_lib.nh_medium_query(self._h, medium, mode, len(inp), _fptr(inp), _fptr(out)), "medium_query")
+        return out[:, 0] if n_out == 1 else out
 
     def trace(self, o: np.ndarray, d: np.ndarray, mint: np.ndarray, maxt: np.ndarray, any_hit=False,
               traversal: int = TRAVERSAL_REFERENCE) -> dict:
