@@ -238,6 +238,10 @@ typedef struct nh_denoiser {
     int32_t amount;          /* passes */
 } nh_denoiser;
 
+/* <sampler> types: independent (src/samplers/independent.cpp) and adaptive (src/samplers/adaptive.cpp). Both take
+ * per-path pcg32 streams on the HIP path; an adaptive scene renders through the adaptive loop of nh_render. */
+enum { NH_SAMPLER_INDEPENDENT = 0, NH_SAMPLER_ADAPTIVE = 1 };
+
 typedef struct nh_scene_desc {
     nh_camera camera;
     nh_filter filter;
@@ -277,6 +281,10 @@ typedef struct nh_scene_desc {
     const uint32_t *shape_medium; /* n_shapes entries: 1 + index into media of the shape's <medium>, 0 = none; may be
                                      NULL (no shape has a medium) */
     uint32_t ambient_medium;      /* 1 + index into media of the scene's ambient <medium>, 0 = vacuum */
+    /* Appended: the scene's <sampler>. A zero-filled tail means the independent sampler. */
+    int32_t sampler;                   /* NH_SAMPLER_* */
+    int32_t adaptive_initial_uniform;  /* NH_SAMPLER_ADAPTIVE: initialUniform after AdaptiveSampler's clamp to
+                                          [1, sampleCount] (src/samplers/adaptive.cpp:21); below 1 counts as 1 */
 } nh_scene_desc;
 
 /* ---- BVH in the reference's own layout (include/nori/bvh.h:127-165) ---- */
@@ -423,6 +431,9 @@ int nh_scene_get_desc(const nh_scene *scene, nh_scene_desc *out);
 /* overrides used by benchmarks and tests (camera resize recomputes the projection) */
 int nh_scene_set_resolution(nh_scene *scene, int32_t width, int32_t height);
 int nh_scene_set_sample_count(nh_scene *scene, int32_t spp);
+/* the scene's sampler: NH_SAMPLER_INDEPENDENT, or NH_SAMPLER_ADAPTIVE with its initialUniform (clamped to
+   [1, sampleCount] as the reference's constructor does; set the sample count first) */
+int nh_scene_set_sampler(nh_scene *scene, int32_t type, int32_t initial_uniform);
 int nh_scene_set_bsdf(nh_scene *scene, uint32_t shape, const nh_bsdf *bsdf);
 /* append a texture to the scene's texture table (png: texels = width*height*4 floats, copied); returns its
    index + 1 for nh_bsdf.albedo_texture, or 0 on error (nh_host_last_error) */
@@ -472,7 +483,29 @@ void nh_destroy(nh_ctx *ctx);
 int nh_upload_scene(nh_ctx *ctx, const nh_scene_desc *scene);
 int nh_upload_bvh(nh_ctx *ctx, const nh_bvh_desc *bvh);
 int nh_trace_rays(nh_ctx *ctx, const nh_ray_soa *rays, int32_t n, int32_t any_hit, int32_t traversal, nh_hit_soa *out);
+/* A scene with the adaptive sampler (nh_scene_desc.sampler == NH_SAMPLER_ADAPTIVE) renders through the adaptive loop
+ * (src/utils/render.cpp:323-336 in the reference's single-thread order): sample_begin..sample_end
+ * count outer samples, every 4x4 block running passes of size.x * size.y paths until its variance test stops it; mode
+ * and traversal change nothing visible. Refused: blocks != NULL, a range that neither starts at 0 nor continues the
+ * previous call's (the blocks' index streams live across calls), a thin-lens camera, a filter wider than border 2,
+ * sample_end beyond NH_ADAPTIVE_MAX_SAMPLES (the int32 path sample index (s * 1002 + pass) * 16 + i), and a render
+ * whose staged block images (1 KiB per block and pass of one outer sample) exceed NH_ADAPTIVE_STAGING_BYTES
+ * (NH_ADAPTIVE_STAGING_MB overrides it): the framebuffer then holds the outer samples before the refused one. */
+#define NH_ADAPTIVE_MAX_SAMPLES 133948
+#define NH_ADAPTIVE_STAGING_BYTES ((size_t)4 << 30)
 int nh_render(nh_ctx *ctx, const nh_render_req *req);
+/* Adaptive renders since the last range that started at 0 (render.cpp:373 "Total Samples Placed") */
+typedef struct nh_adaptive_stats {
+    uint64_t total_samples;       /* size.x * size.y per pass, summed */
+    uint64_t passes;              /* passes summed over blocks and outer samples */
+    uint64_t max_passes;          /* the most passes one block ran in one outer sample (at most 1001) */
+    uint64_t n_blocks;            /* 4x4 blocks of the image */
+} nh_adaptive_stats;
+int nh_get_adaptive_stats(nh_ctx *ctx, nh_adaptive_stats *out);
+/* m_oldVariance of every block at its place in the image (AdaptiveSampler::writeVarianceMatrix): width * height floats,
+   row-major. The reference writes it through Color4f(v), whose weight is v itself, so its <scene>_variance.exr shows 1
+   where this is non-zero. */
+int nh_get_adaptive_variance(nh_ctx *ctx, float *out, size_t n_floats);
 int nh_synchronize(nh_ctx *ctx);
 int nh_get_framebuffer(nh_ctx *ctx, float *rgbw, size_t n_floats);
 /* device pointer of the (W+2b)(H+2b)x4 fp32 framebuffer, for collectives issued by the caller;

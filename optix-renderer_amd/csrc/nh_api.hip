@@ -66,6 +66,7 @@ void nh_destroy(nh_ctx *c) {
     (void)hipFree(c->counters);
     (void)hipFree(c->d_scene);
     for (WfPool &p : c->pools) pool_free(p);
+    adaptive_release(c);
     c->comms.reset();  // the communicators go with the last context of their set
     if (c->fb_ev) (void)hipEventDestroy(c->fb_ev);
     if (c->stream) (void)hipStreamDestroy(c->stream);

@@ -116,6 +116,23 @@ struct PixelList {
     }
 };
 
+// The adaptive sampler's state (nh_adaptive_api.hip): the blocks' sampler clones live from the outer sample 0 of a
+// render to the end of the ranges that continue it, as the reference's samplers vector does
+struct AdaptiveState {
+    int n_blocks = 0, nbx = 0, nby = 0;
+    int next_sample = -1;  // the outer sample a continuing nh_render must start at (-1: only 0 will do)
+    int4 *blocks = nullptr;
+    int *block_rank = nullptr, *active_list = nullptr, *next = nullptr;
+    AdBlock *state = nullptr;
+    unsigned *counts = nullptr, *h_count = nullptr;  // per-pass active counts; pinned copy of the one just decided
+    int2 *pos = nullptr;
+    float4 *rad = nullptr, *staging = nullptr;
+    float2 *jit = nullptr;
+    size_t slot_cap = 0;  // staging slots (and next entries) allocated
+    unsigned long long *stats = nullptr;
+    std::vector<int4> h_blocks;  // by rank
+};
+
 struct nh_ctx {
     uint64_t id = 0;  // unique per context (process lifetime): identifies comm-set members
     std::shared_ptr<CommSet> comms;
@@ -153,6 +170,8 @@ struct nh_ctx {
     bool diffuse_area = false;
     // a shape without a BSDF / a non-vacuum medium: only the volumetric integrators render the scene (nh_render)
     bool bsdfless = false, has_media = false;
+    int sampler = 0, adaptive_initial_uniform = 0;  // NH_SAMPLER_*; an adaptive scene renders through render_adaptive
+    AdaptiveState ad;
     // host copies of the scene tables and the emit_faces count, for the LDS image of a small scene (build_small_image)
     std::vector<nhd::DShape> h_shapes;
     std::vector<nhd::DBsdf> h_bsdfs;
@@ -191,6 +210,10 @@ struct nh_ctx {
 void pool_free(WfPool &p);
 int pipeline_drain(nh_ctx *c);  // runs every submitted chunk to completion
 int check_device(nh_ctx *c, const char *where);
+// nh_adaptive_api.hip: nh_render of a scene with the adaptive sampler (the request already validated as far as
+// every scene's is, the pipeline drained); release of its buffers (nh_destroy, and every scene upload)
+int render_adaptive(nh_ctx *c, const nh_render_req *q);
+void adaptive_release(nh_ctx *c);
 // nh_upload.hip: the DDisney side record of a Disney BSDF (nh_bsdf_query builds one too)
 nhd::DDisney disney_record(const nh_bsdf &b);
 void disney_set_record(nhd::DBsdf &o, const nhd::DDisney *rec);

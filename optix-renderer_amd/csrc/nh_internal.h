@@ -309,3 +309,57 @@ struct MediumQuery {
 void launch_medium_query(const nhd::DScene *S, const MediumQuery &q, hipStream_t st);
 }  // namespace nh
 }  // namespace nh_disney
+
+// ---- the adaptive sampler's render loop (nh_adaptive.hip, driven by nh_adaptive_api.hip) ----
+constexpr int kAdBlock = 4;          // NORI_BLOCK_SIZE_ADAPTIVE (block.h:31)
+constexpr int kAdPaths = 16;         // paths of a pass of a full block
+constexpr int kAdPassStride = 1002;  // sample indices per outer sample: (s * 1002 + pass) * 16 + i
+constexpr int kAdMaxRound = 1000;    // adaptive.cpp:78
+constexpr int kAdMaxBorder = 2;      // a block image is at most 8 x 8: one lane per pixel in the put kernel
+constexpr int kAdImagePx = 64;       // float4 entries of one staged (block, pass) image, row pitch 8
+// One block's AdaptiveSampler clone plus the chain of its staged passes of the outer sample in flight
+struct AdBlock {
+    uint64_t rng_state, rng_inc;  // m_random: seed(offset.x, offset.y) once, then only the index draws
+    float old_var[16];            // m_oldVariance, entry (i, j) at i * 4 + j
+    float old_norm;               // m_oldNorm
+    int active;                   // still rendering passes of this outer sample
+    int npass;                    // passes staged this outer sample
+    int head, last;               // first / latest staging slot of those passes (AdaptiveLaunch::next chains them)
+    int pad;
+};
+struct AdaptiveLaunch {
+    int n_blocks, nbx, nby;       // 4x4 blocks, indexed by BlockGenerator spiral rank below
+    int width, height, border, initial_uniform;
+    int s, k;                     // outer sample, pass
+    uint64_t seed;
+    const int4 *blocks;           // (offset x, offset y, size x, size y) by rank
+    const int *block_rank;        // rank of block id by * nbx + bx
+    AdBlock *state;               // by rank
+    int *active_list;             // ranks of the blocks rendering pass k, in no particular order
+    unsigned *counts;             // [pass]: blocks rendering it (the host reads one per pass)
+    int n_active;                 // counts[k], as the host read it (path, put)
+    int2 *pos;                    // [rank * 16 + i]: the chosen positions of pass k, image coordinates
+    float4 *rad;                  // [active index * 16 + i]: (r, g, b, -) of path i
+    float2 *jit;                  // its pixel jitter
+    float4 *staging;              // kAdImagePx entries per slot
+    int *next;                    // slot -> the slot of the same block's next pass
+    int slot_base;                // slot of active index 0 of pass k
+    unsigned long long *stats;    // [0] samples placed, [1] passes, [2] the most passes of a block in an outer sample
+    float *fb;                    // master RGBW
+    float radius, lookup;
+    float table[33];
+};
+namespace nh_disney {
+namespace nh {
+// the variance test of pass k per block (AdaptiveSampler::computeVariance) and, for the blocks that go on, the pass's
+// positions (getSampleIndices)
+void launch_adaptive_decide(const AdaptiveLaunch &A, hipStream_t st);
+// renderBlock's per-sample body over the explicit position list: the integrator's Li, built with every BSDF and
+// emitter type; closest hits nearer child first whatever the request's traversal
+void launch_adaptive_paths(const nhd::DScene *S, const nhd::Traversal &tv, const AdaptiveLaunch &A, int depth, hipStream_t st);
+// ImageBlock::put of the pass's samples in list order into one staged image per active block
+void launch_adaptive_put(const AdaptiveLaunch &A, hipStream_t st);
+// m_block.put(block) of every staged pass of the outer sample, per master pixel in the serial order
+void launch_adaptive_merge(const AdaptiveLaunch &A, hipStream_t st);
+}  // namespace nh
+}  // namespace nh_disney

@@ -460,6 +460,7 @@ __global__ __launch_bounds__(BLOCK, MINW) void nh_path_kernel(const DScene *__re
     if (STATS) flush_stats(st, queries, stat_shard(L.counters));
 }
 
+#ifndef NH_DEVICE_FUNCTIONS_ONLY  // (nh_adaptive.hip includes this file for the li_* functions above)
 // ---------------------------------------------------------------------------
 // host-side launchers (called from nh_api.hip and nh_pipeline.hip)
 // ---------------------------------------------------------------------------
@@ -560,6 +561,7 @@ void launch_path(const DScene *S, const Traversal &tv, const PathLaunch &L, bool
 }
 
 }  // namespace nh
+#endif  // NH_DEVICE_FUNCTIONS_ONLY
 
 #ifdef NH_DISNEY
 }  // namespace nh_disney

@@ -806,8 +806,11 @@ int nh_render(nh_ctx *c, const nh_render_req *q) {
     HIP_TRY(c, hipSetDevice(c->device));
     // only asynchronous wavefront renders overlap earlier chunks still in flight
     int rc = NH_OK;
-    if (!wavefront || q->collect_stats || q->clear) rc = pipeline_drain(c);
+    if (!wavefront || q->collect_stats || q->clear || c->sampler == NH_SAMPLER_ADAPTIVE) rc = pipeline_drain(c);
     if (rc) return rc;
+    // <sampler type="adaptive">: its own loop of passes over 4x4 blocks (nh_adaptive_api.hip); mode and traversal
+    // change nothing there
+    if (c->sampler == NH_SAMPLER_ADAPTIVE) return render_adaptive(c, q);
     rc = ensure_pixel_list(c, q);
     if (rc) return rc;
     c->stats.node_bytes = 64;  // binary tree unless a wavefront pool picks the 4-wide one

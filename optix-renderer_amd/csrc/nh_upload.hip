@@ -426,6 +426,12 @@ int nh_upload_scene(nh_ctx *c, const nh_scene_desc *d) {
     c->filter = d->filter;
     c->n_emitters = (int)d->n_emitters;
     c->integrator = S.integrator;
+    // (appended fields: a zero-filled tail is the independent sampler)
+    if (d->sampler != NH_SAMPLER_INDEPENDENT && d->sampler != NH_SAMPLER_ADAPTIVE)
+        return fail(c, "unknown sampler"), NH_ERR_INVALID;
+    c->sampler = d->sampler;
+    c->adaptive_initial_uniform = std::max(1, (int)d->adaptive_initial_uniform);
+    adaptive_release(c);  // block samplers of an earlier scene
 
     // master ImageBlock
     (void)hipFree(c->fb);

@@ -317,6 +317,7 @@ __global__ __launch_bounds__(BLOCK, NH_VOL_WAVES) void nh_vol_path_kernel(const 
     if (STATS) flush_stats(st, queries, stat_shard(L.counters));
 }
 
+#ifndef NH_DEVICE_FUNCTIONS_ONLY  // (nh_adaptive.hip includes this file for li_path_vol above)
 // One thread per query
 struct ArrayDraw {
     const float *u;
@@ -373,4 +374,5 @@ void launch_medium_query(const DScene *S, const MediumQuery &q, hipStream_t st) 
 }
 
 }  // namespace nh
+#endif  // NH_DEVICE_FUNCTIONS_ONLY
 }  // namespace nh_disney

@@ -2,7 +2,8 @@
 // (src/utils/main.cpp:32-114 + RenderThread::renderThreadMain, render.cpp:232-419),
 // rendering the scene's path_mis / path_mats integrator on one MI355X through the
 // C-ABI, applying the scene's <denoiser> (render.cpp:368-369), and writing <scene>.exr next to the input
-// (Bitmap::save, bitmap.cpp:82-110).
+// (Bitmap::save, bitmap.cpp:82-110). A scene with the adaptive sampler also prints "Total Samples Placed" and writes
+// <scene>_variance.exr (render.cpp:373, :392-413).
 //
 //   nori_hip scene.xml [--spp N] [--width W --height H] [--device D] [--ordered] [--pfm out.pfm] [--png]
 // --png also writes <scene>.png as Bitmap::saveToLDR (bitmap.cpp:122-140; the reference's hdrToLdr).
@@ -80,9 +81,27 @@ int main(int argc, char **argv) {
     out += ".exr";
     nh_write_exr(out.c_str(), rgb.data(), W, H);
     if (!pfm.empty()) nh_write_pfm(pfm.c_str(), rgb.data(), W, H);
+    double placed = (double)W * H * desc.sample_count;
+    if (desc.sampler == NH_SAMPLER_ADAPTIVE) {
+        // render.cpp:373 and :392-413: the samples the passes placed, and <scene>_variance.exr. The reference writes
+        // every block's m_oldVariance v as Color4f(v) -- weight v -- through toBitmap's divideByFilterWeight, so
+        // the file holds v / v where |v| > Epsilon and 0 elsewhere
+        nh_adaptive_stats as;
+        if (nh_get_adaptive_stats(ctx, &as)) return die("adaptive stats", nh_last_error(ctx));
+        std::printf("Total Samples Placed: %llu\n", (unsigned long long)as.total_samples);
+        placed = (double)as.total_samples;
+        std::vector<float> var((size_t)W * H), vrgb(3 * (size_t)W * H);
+        if (nh_get_adaptive_variance(ctx, var.data(), var.size())) return die("adaptive variance", nh_last_error(ctx));
+        for (size_t i = 0; i < var.size(); ++i) {
+            const float v = var[i], o = (v > 1e-4f || v < -1e-4f) ? v / v : 0.f;
+            vrgb[3 * i] = vrgb[3 * i + 1] = vrgb[3 * i + 2] = o;
+        }
+        const std::string vout = out.substr(0, out.size() - 4) + "_variance.exr";
+        nh_write_exr(vout.c_str(), vrgb.data(), W, H);
+    }
     double bvh_s = std::chrono::duration<double>(t1 - t0).count();
     double rs = std::chrono::duration<double>(t3 - t2).count();
-    double msps = (double)W * H * desc.sample_count / rs / 1e6;
+    double msps = placed / rs / 1e6;
     std::printf("nori_hip: %dx%d %d spp, BVH %u nodes (%.3f s), render %.3f s = %.2f Msamples/s -> %s\n", W, H,
                 desc.sample_count, bd.n_nodes, bvh_s, rs, msps, out.c_str());
     nh_destroy(ctx);

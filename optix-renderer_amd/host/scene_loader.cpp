@@ -218,6 +218,8 @@ struct SceneData {
     int32_t integrator = NH_INTEGRATOR_PATH_MIS;
     float normals_dir[3] = {0.f, 0.f, 1.f};  // NormalIntegrator's `direction`
     int32_t sample_count = 1;
+    int32_t sampler = NH_SAMPLER_INDEPENDENT;
+    int32_t adaptive_initial_uniform = 0;  // AdaptiveSampler::initialUniform after its clamp (adaptive scenes only)
     std::vector<nh_shape> shapes;
     std::vector<nh_bsdf> bsdfs;
     std::vector<nh_emitter> emitters;
@@ -1020,9 +1022,15 @@ void build_scene(const Obj &scene, const std::string &base_dir, SceneData &sd) {
         } else if (ch.tag == "sampler") {
             if (have_sampler) throw SceneError("there can only be one sampler per scene");
             have_sampler = true;
-            if (ch.type != "independent")
+            if (ch.type != "independent" && ch.type != "adaptive")
                 throw SceneError("sampler \"" + ch.type + "\" is not supported (the HIP path uses per-path pcg32)");
             sd.sample_count = ch.props.get_int("sampleCount", 1);
+            if (ch.type == "adaptive") {
+                // AdaptiveSampler's constructor (adaptive.cpp:18-22): clamp(initialUniform [2], 1, sampleCount)
+                sd.sampler = NH_SAMPLER_ADAPTIVE;
+                const int iu = ch.props.get_int("initialUniform", 2);
+                sd.adaptive_initial_uniform = iu < 1 ? 1 : (iu > sd.sample_count ? sd.sample_count : iu);
+            }
         } else if (ch.tag == "shape") {
             nh_shape sh{};
             sh.emitter = -1;
@@ -1232,6 +1240,8 @@ void fill_desc(const SceneData &sd, nh_scene_desc *d) {
     d->media = sd.media.empty() ? nullptr : sd.media.data();
     d->shape_medium = sd.media.empty() ? nullptr : sd.shape_medium.data();
     d->ambient_medium = sd.ambient_medium;
+    d->sampler = sd.sampler;
+    d->adaptive_initial_uniform = sd.adaptive_initial_uniform;
     d->envmap = sd.envmap;
     d->denoiser = sd.denoiser;
     d->n_vertices = (uint32_t)(sd.V.size() / 3);
@@ -1301,6 +1311,19 @@ int nh_scene_set_resolution(nh_scene *scene, int32_t width, int32_t height) {
 int nh_scene_set_sample_count(nh_scene *scene, int32_t spp) {
     if (!scene || spp <= 0) { nh::set_host_error("invalid sample count"); return NH_ERR_INVALID; }
     scene->data->sample_count = spp;
+    return NH_OK;
+}
+
+int nh_scene_set_sampler(nh_scene *scene, int32_t type, int32_t initial_uniform) {
+    if (!scene || (type != NH_SAMPLER_INDEPENDENT && type != NH_SAMPLER_ADAPTIVE)) {
+        nh::set_host_error("invalid sampler type");
+        return NH_ERR_INVALID;
+    }
+    scene->data->sampler = type;
+    // as AdaptiveSampler's constructor clamps it (adaptive.cpp:21), against the scene's present sampleCount
+    const int32_t n = scene->data->sample_count;
+    scene->data->adaptive_initial_uniform =
+        type == NH_SAMPLER_ADAPTIVE ? (initial_uniform < 1 ? 1 : (initial_uniform > n ? n : initial_uniform)) : 0;
     return NH_OK;
 }
 

@@ -48,6 +48,8 @@ MODE_MEGAKERNEL, MODE_WAVEFRONT = 0, 1
 SMALL_TABLES_BYTES = 4096  # NH_SMALL_TABLES_BYTES: LDS budget of the scene tables of the diffuse area-light kernels
 TRAVERSAL_REFERENCE, TRAVERSAL_ORDERED, TRAVERSAL_WIDE = 0, 1, 2
 DENOISER_NONE, DENOISER_SIMPLE = 0, 1
+SAMPLER_INDEPENDENT, SAMPLER_ADAPTIVE = 0, 1  # independent.cpp, adaptive.cpp
+ADAPTIVE_MAX_SAMPLES = 133948  # NH_ADAPTIVE_MAX_SAMPLES
 LENS_DRAWS_LTR, LENS_DRAWS_RTL = 0, 1
 
 _f = C.c_float
@@ -147,7 +149,7 @@ class nh_scene_desc(C.Structure):
                 ("textures", C.POINTER(nh_texture)), ("n_texels", C.c_uint64), ("texels", _fp),
                 ("normals_direction", _f * 3), ("emitter_ext", C.POINTER(nh_emitter_ext)),
                 ("n_media", _u32), ("media", C.POINTER(nh_medium)), ("shape_medium", _u32p),
-                ("ambient_medium", _u32)]
+                ("ambient_medium", _u32), ("sampler", _i32), ("adaptive_initial_uniform", _i32)]
 
 
 class nh_bvh_node(C.Structure):
@@ -173,6 +175,11 @@ class nh_render_req(C.Structure):
     _fields_ = [("sample_begin", _i32), ("sample_end", _i32), ("seed", C.c_uint64), ("n_blocks", _i32),
                 ("blocks", C.POINTER(_i32)), ("mode", _i32), ("traversal", _i32), ("clear", _i32),
                 ("collect_stats", _i32)]
+
+
+class nh_adaptive_stats(C.Structure):
+    _fields_ = [("total_samples", C.c_uint64), ("passes", C.c_uint64), ("max_passes", C.c_uint64),
+                ("n_blocks", C.c_uint64)]
 
 
 class nh_render_stats(C.Structure):
@@ -213,6 +220,7 @@ _sig("nh_scene_load_xml_index", _i32, C.c_char_p, _i32, C.POINTER(_vp))
 _sig("nh_scene_get_desc", _i32, _vp, C.POINTER(nh_scene_desc))
 _sig("nh_scene_set_resolution", _i32, _vp, _i32, _i32)
 _sig("nh_scene_set_sample_count", _i32, _vp, _i32)
+_sig("nh_scene_set_sampler", _i32, _vp, _i32, _i32)
 _sig("nh_scene_set_bsdf", _i32, _vp, _u32, C.POINTER(nh_bsdf))
 _sig("nh_scene_set_integrator", _i32, _vp, _i32)
 _sig("nh_scene_add_texture", _u32, _vp, C.POINTER(nh_texture), _fp)
@@ -243,6 +251,8 @@ _sig("nh_get_framebuffer", _i32, _vp, _fp, C.c_size_t)
 _sig("nh_framebuffer_device_ptr", _i32, _vp, C.POINTER(_vp), C.POINTER(C.c_size_t))
 _sig("nh_get_stats", _i32, _vp, C.POINTER(nh_render_stats))
 _sig("nh_reset_stats", _i32, _vp)
+_sig("nh_get_adaptive_stats", _i32, _vp, C.POINTER(nh_adaptive_stats))
+_sig("nh_get_adaptive_variance", _i32, _vp, _fp, C.c_size_t)
 _sig("nh_reduce_framebuffers", _i32, C.POINTER(_vp), _i32, _i32)
 _sig("nh_denoise", _i32, _vp, C.POINTER(nh_denoiser))
 _sig("nh_denoise_image", _i32, _vp, _fp, _i32, _i32, _i32, C.POINTER(nh_denoiser))
@@ -303,6 +313,11 @@ class Scene:
 
     def set_sample_count(self, spp: int):
         _host_check(_lib.nh_scene_set_sample_count(self._h, spp), "set_sample_count")
+
+    def set_sampler(self, type: int, initial_uniform: int = 2):
+        """SAMPLER_INDEPENDENT, or SAMPLER_ADAPTIVE with its initialUniform (clamped to [1, sampleCount] as
+        AdaptiveSampler's constructor does: set the sample count first)."""
+        _host_check(_lib.nh_scene_set_sampler(self._h, type, initial_uniform), "set_sampler")
 
     def set_integrator(self, integ: int):
         _host_check(_lib.nh_scene_set_integrator(self._h, integ), "set_integrator")
@@ -521,6 +536,19 @@ class Context:
         s = nh_render_stats()
         self._check(_lib.nh_get_stats(self._h, C.byref(s)), "get_stats")
         return {f: getattr(s, f) for f, _ in s._fields_}
+
+    def adaptive_stats(self) -> dict:
+        """nh_get_adaptive_stats: total_samples ("Total Samples Placed"), passes, max_passes, n_blocks of the
+        adaptive renders since the last range that started at 0."""
+        s = nh_adaptive_stats()
+        self._check(_lib.nh_get_adaptive_stats(self._h, C.byref(s)), "get_adaptive_stats")
+        return {f: int(getattr(s, f)) for f, _ in s._fields_}
+
+    def adaptive_variance(self) -> np.ndarray:
+        """nh_get_adaptive_variance: every block's m_oldVariance at its place in the image, (H, W) float32."""
+        out = np.zeros((self.scene.height, self.scene.width), np.float32)
+        self._check(_lib.nh_get_adaptive_variance(self._h, _fptr(out), out.size), "get_adaptive_variance")
+        return out
 
     def reset_stats(self):
         self._check(_lib.nh_reset_stats(self._h), "reset_stats")
