@@ -36,15 +36,13 @@ HIP_OBJ  := $(patsubst $(PKG)/csrc/%.hip,$(OBJDIR)/hip_%.o,$(HIP_SRC)) \
 # those lights never launch these (nh_ctx.h NH_LAUNCH). Only what shades is built: parts 0 and 3 (traversal kernels) and
 # part 4 (the diffuse area-light instantiations) have no variant, and parts 1 and 2 leave their other kernels out.
 # nh_volume.hip (the volumetric path tracers and the medium query) is built this way only: one copy, with every BSDF
-# and emitter type. So is nh_adaptive.hip (the adaptive sampler's kernels), which includes the integrators' device
-# functions from nh_kernels.hip and nh_volume.hip.
+# and emitter type. So is nh_adaptive.hip (the adaptive sampler's kernels). The integrators themselves are device
+# function templates in headers (nh_integrators.h, nh_volume.h), shared by the three units.
 DZ_PARTS := 1 2
 HIP_OBJ  += $(OBJDIR)/hipdz_nh_kernels.o $(OBJDIR)/hipdz_nh_disney.o $(OBJDIR)/hipdz_nh_emitter_query.o \
             $(OBJDIR)/hipdz_nh_volume.o $(OBJDIR)/hipdz_nh_adaptive.o \
             $(foreach k,$(DZ_PARTS),$(OBJDIR)/hipdz_nh_wavefront_p$(k).o)
 HIP_DEPS := $(wildcard $(PKG)/csrc/*.h) $(PKG)/host/gpu_layout.h include/nori_hip.h
-# (nh_adaptive.hip includes these two)
-$(OBJDIR)/hipdz_nh_adaptive.o: $(PKG)/csrc/nh_kernels.hip $(PKG)/csrc/nh_volume.hip
 # The wavefront kernels build without LLVM's machine-level LICM: it hoists loop invariants out of the traversal, bounce
 # and tail loops into registers for the loop's whole length, which then spill (wf_tail_rr at 4 waves/SIMD: 448 ->
 # 28 B/lane of scratch; wf_tail 256 -> 157 VGPRs; the persistent traversals 96 -> 88). C5 +3.6 %, other configs
@@ -61,8 +59,9 @@ VALUBENCH := tools/bin/valu_issue
 
 MANUAL   := tests/c/bin/manual_scene
 LAYOUTCHECK := tests/c/bin/gpu_layout_check
+DISPATCHCHECK := tests/c/bin/dispatch_check
 
-all: $(LIB) $(HOSTLIB) $(ORACLE) $(CLI) $(RCPCHECK) $(VALUBENCH) $(MANUAL) $(LAYOUTCHECK)
+all: $(LIB) $(HOSTLIB) $(ORACLE) $(CLI) $(RCPCHECK) $(VALUBENCH) $(MANUAL) $(LAYOUTCHECK) $(DISPATCHCHECK)
 
 # C test: a scene description filled field by field (no XML loader), rendered through the C-ABI and
 # compared with the oracle (run by tests/test_gpu_parity.py)
@@ -76,6 +75,12 @@ $(MANUAL): tests/c/manual_scene.c $(LIB) $(ORACLE) include/nori_hip.h oracle/nor
 $(LAYOUTCHECK): tests/c/gpu_layout_check.cpp $(HOSTLIB) $(PKG)/host/gpu_layout.h $(PKG)/csrc/nh_layout.h include/nori_hip.h
 	@mkdir -p tests/c/bin
 	$(CXX) $(HOST_FLAGS) -I$(PKG)/csrc -o $@ $< -L$(LIBDIR) -lnori_host -Wl,-rpath,'$$ORIGIN/../../../$(LIBDIR)'
+
+# C++ test: the launchers' flag / depth dispatch helpers (csrc/nh_dispatch.h) on the CPU, no HIP (run by
+# tests/test_dispatch_host.py)
+$(DISPATCHCHECK): tests/c/dispatch_check.cpp $(PKG)/csrc/nh_dispatch.h
+	@mkdir -p tests/c/bin
+	$(CXX) -std=c++17 -O2 -Wall -Wextra -I$(PKG)/csrc -o $@ $<
 
 # exhaustive check of the fast reciprocal the traversal kernels use (run by the GPU tests)
 $(RCPCHECK): tools/rcp_exhaustive.hip $(HIP_DEPS)

@@ -8,7 +8,7 @@
 //                      linear vectorised redux; DiscretePDF), then either the block retires or getSampleIndices writes
 //                      the pass's positions -- uniform, or drawn from the block's own pcg32 stream
 //   ad_path_kernel     renderBlock's per-sample body over that explicit list: per-path stream, pixel jitter, camera
-//                      ray and the integrator's Li (the li_* functions of nh_kernels.hip, li_path_vol of nh_volume.hip)
+//                      ray and the integrator's Li (the li_* functions of nh_integrators.h, li_path_vol of nh_volume.h)
 //   ad_put_kernel      ImageBlock::put(pos, value) of the pass's samples in list order into the block's own image, one
 //                      64-lane wave per block, one lane per pixel of the (at most) 8x8 image, staged per (block, pass)
 //
@@ -20,14 +20,10 @@
 // No kernel waits for another workgroup; the host reads one count per pass (the blocks still rendering).
 //
 // Built once, with -DNH_DISNEY (Makefile), as nh_volume.hip is: every BSDF and emitter type the HIP path has. The
-// integrators are the device functions the megakernels call, included from their files; no existing kernel changes.
-#define NH_DEVICE_FUNCTIONS_ONLY 1
-#include "nh_kernels.hip"
-#include "nh_volume.hip"
-
-#ifndef NH_DISNEY
-#error "nh_adaptive.hip is built with -DNH_DISNEY"
-#endif
+// integrators are the device functions the megakernels call (nh_integrators.h, nh_volume.h).
+#include "nh_dispatch.h"
+#include "nh_integrators.h"
+#include "nh_volume.h"
 
 namespace nh_disney {
 
@@ -322,9 +318,9 @@ void launch_adaptive_decide(const AdaptiveLaunch &A, hipStream_t st) {
 void launch_adaptive_paths(const DScene *S, const Traversal &tv, const AdaptiveLaunch &A, int depth, hipStream_t st) {
     if (A.n_active <= 0) return;
     const dim3 grid(((size_t)A.n_active * kAdPaths + 63) / 64);
-    if (depth <= 32) hipLaunchKernelGGL((ad_path_kernel<32>), grid, dim3(64), 0, st, S, tv, A);
-    else if (depth <= 64) hipLaunchKernelGGL((ad_path_kernel<64>), grid, dim3(64), 0, st, S, tv, A);
-    else hipLaunchKernelGGL((ad_path_kernel<128>), grid, dim3(64), 0, st, S, tv, A);
+    nh_dispatch_depth<32, 64, 128>(depth, [&](auto d) {
+        hipLaunchKernelGGL((ad_path_kernel<d>), grid, dim3(64), 0, st, S, tv, A);
+    });
 }
 
 void launch_adaptive_put(const AdaptiveLaunch &A, hipStream_t st) {

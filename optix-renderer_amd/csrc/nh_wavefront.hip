@@ -26,6 +26,7 @@
 //
 // Each path's random numbers come from its own pcg32 stream in the reference's draw order,
 // so the wavefront and megakernel renders are identical.
+#include "nh_dispatch.h"
 #include "nh_internal.h"
 #include "nh_shade.h"
 
@@ -1693,36 +1694,23 @@ static void launch_wf_trace_d(const DScene *S, const Traversal &tv, const WfLaun
     const int want = std::max(1, (bound + 127) / 128);
     const dim3 grid(std::min(want, persistent ? kPersistentBlocks : kTraceBlocksMax));
     if (persistent) {
-#define NH_PT(A, O, T)                                                                               \
-    do {                                                                                             \
-        if (wide == 8) { if constexpr (O) launch_persistent<wf_trace_pt<DEPTH, O, A, T, 8>>(want, st, S, tv, L); } \
-        else if (wide) launch_persistent<wf_trace_pt<DEPTH, O, A, T, 4>>(want, st, S, tv, L);              \
-        else launch_persistent<wf_trace_pt<DEPTH, O, A, T, 0>>(want, st, S, tv, L);                  \
-    } while (0)
-        if (shadow) {
-            if (ordered) { if (stats) NH_PT(true, true, true); else NH_PT(true, true, false); }
-            else { if (stats) NH_PT(true, false, true); else NH_PT(true, false, false); }
-        } else {
-            if (ordered) { if (stats) NH_PT(false, true, true); else NH_PT(false, true, false); }
-            else { if (stats) NH_PT(false, false, true); else NH_PT(false, false, false); }
-        }
-#undef NH_PT
+        nh_dispatch([&](auto A, auto O, auto T) {
+            if (wide == 8) {  // no left-first 8-wide kernel is built
+                if constexpr (O) launch_persistent<wf_trace_pt<DEPTH, O, A, T, 8>>(want, st, S, tv, L);
+            } else if (wide) launch_persistent<wf_trace_pt<DEPTH, O, A, T, 4>>(want, st, S, tv, L);
+            else launch_persistent<wf_trace_pt<DEPTH, O, A, T, 0>>(want, st, S, tv, L);
+        }, shadow, ordered, stats);
         return;
     }
     const bool small = DEPTH == 16 && L.small_nodes + L.small_prims > 0;
     const size_t lds = small ? 16 * (size_t)(L.small_nodes + L.small_prims) + 8 * (size_t)L.small_leaves : 0;
-#define NH_WF2(K, O, T, SM) hipLaunchKernelGGL((K<DEPTH, O, T, SM>), grid, dim3(128), lds, st, S, tv, L)
-#define NH_WF(K, O, T) { if constexpr (DEPTH == 16) { if (small) NH_WF2(K, O, T, true); else NH_WF2(K, O, T, false); } \
-                         else NH_WF2(K, O, T, false); }
-    if (shadow) {
-        if (ordered) { if (stats) NH_WF(wf_shadow, true, true) else NH_WF(wf_shadow, true, false) }
-        else { if (stats) NH_WF(wf_shadow, false, true) else NH_WF(wf_shadow, false, false) }
-    } else {
-        if (ordered) { if (stats) NH_WF(wf_extend, true, true) else NH_WF(wf_extend, true, false) }
-        else { if (stats) NH_WF(wf_extend, false, true) else NH_WF(wf_extend, false, false) }
-    }
-#undef NH_WF2
-#undef NH_WF
+    nh_dispatch([&](auto A, auto O, auto T, auto SM) {
+        // the copies that read the scene from LDS (SMALL) exist at DEPTH == 16 only (`small` is false elsewhere)
+        if constexpr (!SM || DEPTH == 16) {
+            if constexpr (A) hipLaunchKernelGGL((wf_shadow<DEPTH, O, T, SM>), grid, dim3(128), lds, st, S, tv, L);
+            else hipLaunchKernelGGL((wf_extend<DEPTH, O, T, SM>), grid, dim3(128), lds, st, S, tv, L);
+        }
+    }, shadow, ordered, stats, small);
 }
 
 #endif
@@ -1746,64 +1734,49 @@ void launch_wf_trace_deep(const DScene *S, const Traversal &tv, const WfLaunch &
 #endif
 
 #if NH_WF_HAS_PART(1)
-template <int DEPTH>
-static void launch_wf_tail_d(const DScene *S, const Traversal &tv, const WfLaunch &L, bool ordered, bool stats,
-                             int wide, int bound, hipStream_t st) {
-    // grid-stride; the wide variant's lanes own spill areas of the persistent grid's size
-    const dim3 grid(std::min(std::max(1, (bound + 127) / 128), wide ? kPersistentBlocks : kTraceBlocksMax));
-    const bool small = DEPTH == 16 && L.small_nodes + L.small_prims > 0;
-    const size_t lds = small ? 16 * (size_t)(L.small_nodes + L.small_prims) + 8 * (size_t)L.small_leaves : 0;
-#define NH_TL2(O, T, SM, W) hipLaunchKernelGGL((wf_tail<DEPTH, O, T, SM, W>), grid, dim3(128), lds, st, S, tv, L)
-#define NH_TLW(O, T) { if (wide == 8) { if constexpr (O) NH_TL2(O, T, false, 8); } \
-                       else if (wide) NH_TL2(O, T, false, 4); else NH_TL2(O, T, false, 0); }
-#define NH_TL(O, T) { if constexpr (DEPTH == 16) { if (small) NH_TL2(O, T, true, 0); else NH_TLW(O, T) } \
-                      else NH_TLW(O, T) }
-    if (ordered) { if (stats) NH_TL(true, true) else NH_TL(true, false) }
-    else { if (stats) NH_TL(false, true) else NH_TL(false, false) }
-#undef NH_TL2
-#undef NH_TLW
-#undef NH_TL
-}
-
 #if !NH_WF_SHADING_ONLY
 void launch_wf_trace2(const DScene *S, const Traversal &tv, const WfLaunch &L, bool ordered, bool stats, int wide,
                       int bound, hipStream_t st) {
     // the wide trees are walked near-first only (nh_pipeline.hip pool_start uses them for ordered traversals)
     (void)ordered;
     const int want = std::max(1, (bound + 127) / 128);
-    if (wide == 8) {
-        if (stats) launch_persistent<wf_trace_pt2<true, true, 8>>(want, st, S, tv, L);
-        else launch_persistent<wf_trace_pt2<true, false, 8>>(want, st, S, tv, L);
-        return;
-    }
-    if (stats) launch_persistent<wf_trace_pt2<true, true>>(want, st, S, tv, L);
-    else launch_persistent<wf_trace_pt2<true, false>>(want, st, S, tv, L);
+    nh_dispatch([&](auto W8, auto T) {
+        if constexpr (W8) launch_persistent<wf_trace_pt2<true, T, 8>>(want, st, S, tv, L);
+        else launch_persistent<wf_trace_pt2<true, T>>(want, st, S, tv, L);
+    }, wide == 8, stats);
 }
 #endif
 
 void launch_wf_tail(const DScene *S, const Traversal &tv, const WfLaunch &L, bool ordered, bool stats, int wide,
                     int bound, int depth, hipStream_t st) {
-    if (depth <= 16) launch_wf_tail_d<16>(S, tv, L, ordered, stats, wide, bound, st);
-    else if (depth <= 32) launch_wf_tail_d<32>(S, tv, L, ordered, stats, wide, bound, st);
-    else if (depth <= 64) launch_wf_tail_d<64>(S, tv, L, ordered, stats, wide, bound, st);
-    else launch_wf_tail_d<128>(S, tv, L, ordered, stats, wide, bound, st);
+    // grid-stride; the wide variant's lanes own spill areas of the persistent grid's size
+    const dim3 grid(std::min(std::max(1, (bound + 127) / 128), wide ? kPersistentBlocks : kTraceBlocksMax));
+    nh_dispatch_depth<16, 32, 64, 128>(depth, [&](auto d) {
+        constexpr int DEPTH = d;
+        const bool small = DEPTH == 16 && L.small_nodes + L.small_prims > 0;
+        const size_t lds = small ? 16 * (size_t)(L.small_nodes + L.small_prims) + 8 * (size_t)L.small_leaves : 0;
+        nh_dispatch([&](auto O, auto T, auto SM) {
+            const auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(128), lds, st, S, tv, L); };
+            // the copy that reads the scene from LDS (SMALL) exists at DEPTH == 16 only (`small` is false elsewhere),
+            // and for the binary tree only
+            if constexpr (SM) {
+                if constexpr (DEPTH == 16) launch(wf_tail<DEPTH, O, T, true, 0>);
+            } else if (wide == 8) {  // no left-first 8-wide kernel is built
+                if constexpr (O) launch(wf_tail<DEPTH, O, T, false, 8>);
+            } else if (wide) launch(wf_tail<DEPTH, O, T, false, 4>);
+            else launch(wf_tail<DEPTH, O, T, false, 0>);
+        }, ordered, stats, small);
+    });
 }
-
 
 void launch_wf_bounce(const DScene *S, const Traversal &tv, const WfLaunch &L, bool ordered, bool stats, bool sort,
                       int bound, hipStream_t st) {
     int blocks = std::max(1, (bound + 255) / 256);
     blocks = (blocks + kQueueShards - 1) / kQueueShards * kQueueShards;
     const size_t lds = 16 * (size_t)rr_lds_f4(L);
-#define NH_FB(O, T, SO) hipLaunchKernelGGL((wf_bounce<O, T, SO>), dim3(blocks), dim3(256), lds, st, S, tv, L)
-    if (ordered) {
-        if (stats) { if (sort) NH_FB(true, true, true); else NH_FB(true, true, false); }
-        else { if (sort) NH_FB(true, false, true); else NH_FB(true, false, false); }
-    } else {
-        if (stats) { if (sort) NH_FB(false, true, true); else NH_FB(false, true, false); }
-        else { if (sort) NH_FB(false, false, true); else NH_FB(false, false, false); }
-    }
-#undef NH_FB
+    nh_dispatch([&](auto O, auto T, auto SO) {
+        hipLaunchKernelGGL((wf_bounce<O, T, SO>), dim3(blocks), dim3(256), lds, st, S, tv, L);
+    }, ordered, stats, sort);
 }
 
 #endif
@@ -1817,25 +1790,15 @@ void launch_wf_bounce_rr(const DScene *S, const Traversal &tv, const WfLaunch &L
     int blocks = std::max(1, (bound + NH_BOUNCE_TB - 1) / NH_BOUNCE_TB);
     blocks = (blocks + kQueueShards - 1) / kQueueShards * kQueueShards;
     const size_t lds = 16 * (size_t)rr_lds_f4(L);
-#define NH_FB(O, T, SO) hipLaunchKernelGGL((wf_bounce_rr<O, T, SO>), dim3(blocks), dim3(NH_BOUNCE_TB), lds, st, S, tv, L)
-#define NH_FBN(T, SO) hipLaunchKernelGGL((wf_bounce_rr<true, T, SO, false>), dim3(blocks), dim3(NH_BOUNCE_TB), lds, st, S, tv, L)
-#define NH_FBF(T, SO) hipLaunchKernelGGL((wf_bounce_rr<true, T, SO, true, false>), dim3(blocks), dim3(NH_BOUNCE_TB), lds, st, S, tv, L)
+    const auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(blocks), dim3(NH_BOUNCE_TB), lds, st, S, tv, L); };
+    // the two trimmed bodies are built for near-first traversal only
     if (ordered && lean) {  // no discrete BSDF, no texture: wf_bounce_rr<.., FULL = false>
-        if (stats) { if (sort) NH_FBN(true, true); else NH_FBN(true, false); }
-        else { if (sort) NH_FBN(false, true); else NH_FBN(false, false); }
+        nh_dispatch([&](auto T, auto SO) { launch(wf_bounce_rr<true, T, SO, false>); }, stats, sort);
     } else if (ordered && !nmap) {  // the full body without normal maps: wf_bounce_rr<.., FULL = true, NMAP = false>
-        if (stats) { if (sort) NH_FBF(true, true); else NH_FBF(true, false); }
-        else { if (sort) NH_FBF(false, true); else NH_FBF(false, false); }
-    } else if (ordered) {
-        if (stats) { if (sort) NH_FB(true, true, true); else NH_FB(true, true, false); }
-        else { if (sort) NH_FB(true, false, true); else NH_FB(true, false, false); }
+        nh_dispatch([&](auto T, auto SO) { launch(wf_bounce_rr<true, T, SO, true, false>); }, stats, sort);
     } else {
-        if (stats) { if (sort) NH_FB(false, true, true); else NH_FB(false, true, false); }
-        else { if (sort) NH_FB(false, false, true); else NH_FB(false, false, false); }
+        nh_dispatch([&](auto O, auto T, auto SO) { launch(wf_bounce_rr<O, T, SO>); }, ordered, stats, sort);
     }
-#undef NH_FB
-#undef NH_FBN
-#undef NH_FBF
 }
 
 void launch_wf_tail_rr(const DScene *S, const Traversal &tv, const WfLaunch &L, bool ordered, bool stats, int bound,
@@ -1850,11 +1813,6 @@ void launch_wf_tail_rr(const DScene *S, const Traversal &tv, const WfLaunch &L, 
     int waves = w ? (std::atoi(w) == 1 ? 1 : std::atoi(w) == 2 ? 2 : 4) : specular ? 1 : 2;
 #ifdef NH_DISNEY  // the 4-wave copies spill in every build and more with Disney's eval: the variant has none
     if (waves == 4) waves = 2;
-#define NH_TR4(O, T)
-#else
-#define NH_TR4(O, T)                                                                                        \
-        else if (lean) hipLaunchKernelGGL((wf_tail_rr<O, T, 64, 4, false>), grid, dim3(64), lds, st, S, tv, L, coop); \
-        else hipLaunchKernelGGL((wf_tail_rr<O, T, 64, 4>), grid, dim3(64), lds, st, S, tv, L, coop);
 #endif
     const char *ln = std::getenv("NH_TAIL_LEAN");
     if (ln && ln[0] == '0') lean = false;
@@ -1867,21 +1825,19 @@ void launch_wf_tail_rr(const DScene *S, const Traversal &tv, const WfLaunch &L, 
     // one path per lane: the grid covers the bound (tail bounds are <= kTailCap paths)
     const dim3 grid(std::max(1, (bound + tb - 1) / tb));
     const size_t lds = 16 * (size_t)rr_lds_f4(L);
-#define NH_TR(O, T)                                                                                         \
-    do {                                                                                                    \
-        if (tb == 256) hipLaunchKernelGGL((wf_tail_rr<O, T, 256, 1>), grid, dim3(256), lds, st, S, tv, L, coop); \
-        else if (waves == 1 && !nmap && O)                                                                  \
-            hipLaunchKernelGGL((wf_tail_rr<O, T, 64, 1, true, false>), grid, dim3(64), lds, st, S, tv, L, coop); \
-        else if (waves == 1) hipLaunchKernelGGL((wf_tail_rr<O, T, 64, 1>), grid, dim3(64), lds, st, S, tv, L, coop); \
-        else if (lean && waves == 2)                                                                        \
-            hipLaunchKernelGGL((wf_tail_rr<O, T, 64, 2, false>), grid, dim3(64), lds, st, S, tv, L, coop);  \
-        else if (waves == 2) hipLaunchKernelGGL((wf_tail_rr<O, T, 64, 2>), grid, dim3(64), lds, st, S, tv, L, coop); \
-        NH_TR4(O, T)                                                                                        \
-    } while (0)
-    if (ordered) { if (stats) NH_TR(true, true); else NH_TR(true, false); }
-    else { if (stats) NH_TR(false, true); else NH_TR(false, false); }
-#undef NH_TR
-#undef NH_TR4
+    const auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(tb), lds, st, S, tv, L, coop); };
+    nh_dispatch([&](auto O, auto T) {
+        if (tb == 256) launch(wf_tail_rr<O, T, 256, 1>);
+        // (the copy without normal maps is launched for near-first traversal only; its left-first one is built as well)
+        else if (waves == 1 && !nmap && O) launch(wf_tail_rr<O, T, 64, 1, true, false>);
+        else if (waves == 1) launch(wf_tail_rr<O, T, 64, 1>);
+        else if (lean && waves == 2) launch(wf_tail_rr<O, T, 64, 2, false>);
+        else if (waves == 2) launch(wf_tail_rr<O, T, 64, 2>);
+#ifndef NH_DISNEY  // (the variant has no 4-wave copies, see above)
+        else if (lean) launch(wf_tail_rr<O, T, 64, 4, false>);
+        else launch(wf_tail_rr<O, T, 64, 4>);
+#endif
+    }, ordered, stats);
 }
 
 #endif
@@ -1892,23 +1848,20 @@ void launch_wf_bounce_trait(const DScene *S, const Traversal &tv, const WfLaunch
     int blocks = std::max(1, (bound + NH_BOUNCE_TB - 1) / NH_BOUNCE_TB);
     blocks = (blocks + kQueueShards - 1) / kQueueShards * kQueueShards;
     const size_t lds = 16 * (size_t)rr_lds_f4(L);
-#define NH_FBT(T, B) \
-    hipLaunchKernelGGL((wf_bounce_rr<true, T, false, false, false, true, B>), dim3(blocks), dim3(NH_BOUNCE_TB), lds, st, S, tv, L)
-#if NH_TRAIT_SPLIT
-    if (L.first) { if (stats) NH_FBT(true, 0); else NH_FBT(false, 0); }
-    else { if (stats) NH_FBT(true, 1); else NH_FBT(false, 1); }
-#else
-    if (stats) NH_FBT(true, -1); else NH_FBT(false, -1);
-#endif
-#undef NH_FBT
+    nh_dispatch([&](auto FIRST, auto T) {
+        constexpr int BOUNCE = NH_TRAIT_SPLIT ? (FIRST ? 0 : 1) : -1;  // bounce 0 / the later ones, or one copy for both
+        hipLaunchKernelGGL((wf_bounce_rr<true, T, false, false, false, true, BOUNCE>), dim3(blocks), dim3(NH_BOUNCE_TB),
+                           lds, st, S, tv, L);
+    }, L.first != 0, stats);
 }
 
 void launch_wf_tail_trait(const DScene *S, const Traversal &tv, const WfLaunch &L, bool stats, int bound, int coop,
                           hipStream_t st) {
     const dim3 grid(std::max(1, (bound + 63) / 64));
     const size_t lds = 16 * (size_t)rr_lds_f4(L);
-    if (stats) hipLaunchKernelGGL((wf_tail_rr<true, true, 64, 2, false, false, true>), grid, dim3(64), lds, st, S, tv, L, coop);
-    else hipLaunchKernelGGL((wf_tail_rr<true, false, 64, 2, false, false, true>), grid, dim3(64), lds, st, S, tv, L, coop);
+    nh_dispatch([&](auto T) {
+        hipLaunchKernelGGL((wf_tail_rr<true, T, 64, 2, false, false, true>), grid, dim3(64), lds, st, S, tv, L, coop);
+    }, stats);
 }
 #endif
 
@@ -1940,10 +1893,9 @@ void launch_wf_shade(const DScene *S, const Traversal &tv, const WfLaunch &L, bo
     // one 256-entry chunk per workgroup up to the bound; a multiple of kQueueShards (see wf_shade)
     int blocks = std::max(1, (bound + 255) / 256);
     blocks = (blocks + kQueueShards - 1) / kQueueShards * kQueueShards;
-    if (sort && nmap) hipLaunchKernelGGL((wf_shade<true>), dim3(blocks), dim3(256), 0, st, S, tv, L);
-    else if (sort) hipLaunchKernelGGL((wf_shade<true, false>), dim3(blocks), dim3(256), 0, st, S, tv, L);
-    else if (nmap) hipLaunchKernelGGL((wf_shade<false>), dim3(blocks), dim3(256), 0, st, S, tv, L);
-    else hipLaunchKernelGGL((wf_shade<false, false>), dim3(blocks), dim3(256), 0, st, S, tv, L);
+    nh_dispatch([&](auto SO, auto NM) {
+        hipLaunchKernelGGL((wf_shade<SO, NM>), dim3(blocks), dim3(256), 0, st, S, tv, L);
+    }, sort, nmap);
 }
 
 #endif
