@@ -565,6 +565,79 @@ int nh_emitter_query(nh_ctx *ctx, uint32_t emitter, int32_t mode, int32_t n, con
 enum { NH_MEDIUM_QUERY_FREE_PATH = 0, NH_MEDIUM_QUERY_TRANSMITTANCE = 1, NH_MEDIUM_QUERY_PHASE_SAMPLE = 2,
        NH_MEDIUM_QUERY_PHASE_PDF = 3 };
 int nh_medium_query(nh_ctx *ctx, uint32_t medium, int32_t mode, int32_t n, const float *in, float *out);
+
+/* ---- the reference's t-test procedure (src/utils/ttest.cpp) and the per-path radiance query ----------------- */
+
+/* A <test> root: StudentsTTest ("ttest") or ChiSquareTest ("chi2test"). The constructor's properties with their
+ * defaults, the `angles` / `references` lists tokenised as ttest.cpp:62-79 (an absent list is the one value 0, as
+ * there: toFloat reads the empty token as 0), the number of <scene> children (each
+ * loads through nh_scene_load_xml_index) and the <bsdf> children. nh_test_load_xml fails (NH_ERR_IO, the reference's
+ * own message in nh_host_last_error) where StudentsTTest's addChild or execute() throw, and with NH_ERR_INVALID on
+ * a file whose root is not a <test>. The pointers live as long as the nh_test. */
+enum { NH_TEST_TTEST = 0, NH_TEST_CHI2TEST = 1 };
+typedef struct nh_test_desc {
+    int32_t type;                 /* NH_TEST_* */
+    float significance_level;     /* significanceLevel [0.01] */
+    int32_t sample_count;         /* sampleCount [ttest: 100000; chi2test: -1] */
+    uint32_t n_angles;
+    const float *angles;
+    uint32_t n_references;
+    const float *references;
+    uint32_t n_scenes;
+    uint32_t n_bsdfs;
+    const nh_bsdf *bsdfs;
+} nh_test_desc;
+typedef struct nh_test nh_test;
+int nh_test_load_xml(const char *path, nh_test **out);
+int nh_test_get_desc(const nh_test *test, nh_test_desc *out);
+void nh_test_free(nh_test *test);
+
+/* hypothesis::students_t_test (ext/hypothesis/hypothesis.h:314-346): t = |mean - reference| sqrt(n / max(variance,
+ * 1e-5)), the two-sided p-value of Student's t with n - 1 degrees of freedom, the Sidak-corrected level
+ * 1 - (1 - alpha)^(1 / num_tests); *accepted = 0 when p < level or p is not finite. p_value may be NULL.
+ * NH_ERR_INVALID for n < 2 or num_tests < 1. Host only. */
+int nh_students_t_test(double mean, double variance, double reference, int32_t n, double alpha, int32_t num_tests,
+                       int32_t *accepted, double *p_value);
+
+/* One path's radiance, by the device functions the render kernels call: entry i is sample sample[i] of pixel
+ * pixel[i] (y * width + x) under `seed` -- the per-path stream path_rng(seed, pixel, sample), two jitter draws, the two
+ * unused aperture draws, the camera ray through (x + jx, y + jy) or through (pixel_sample[2i], pixel_sample[2i + 1])
+ * when pixel_sample is given (the draws are made all the same), a thin-lens camera's lens sample of (pixel, sample) as
+ * in a render, then the Li of the uploaded scene's integrator. rgb (3n) is that radiance as it is: no NaN / negative
+ * filtering (ImageBlock::put's job). jitter (2n, may be NULL): (jx, jy). The scene's sampler type is not read.
+ * Closest hits go nearer child first. n <= 2^24; NH_ERR_INVALID for a pixel outside [0, width * height) or a negative
+ * sample. Needs an uploaded scene and BVH. */
+#define NH_RADIANCE_QUERY_MAX (1 << 24)
+int nh_radiance_query(nh_ctx *ctx, uint64_t seed, int32_t n, const int32_t *pixel, const int32_t *sample,
+                      const float *pixel_sample, float *rgb, float *jitter);
+/* StudentsTTest's scene branch (ttest.cpp:210-230) over samples k = first .. first + n - 1, each on its own stream
+ * path_rng(seed, 0, k): pixelSample = (a * (float)width, b * (float)height) from its first two draws, the two aperture
+ * draws, Li, Color3f::getLuminance in fp32 widened to double; mean and unbiased variance (n >= 2) reduced on the
+ * device in fp64, in an order that depends on n alone. luminance (n floats, may be NULL): every sample's. The
+ * reference draws all samples from one sequential stream; per-sample streams are this library's contract.
+ * A thin-lens camera is refused (NH_ERR_UNSUPPORTED). Needs an uploaded scene and BVH. */
+int nh_ttest_scene(nh_ctx *ctx, uint64_t seed, int64_t first, int32_t n, double *mean, double *variance,
+                   float *luminance);
+/* StudentsTTest's BSDF branch (ttest.cpp:167-181): wi = sphericalDirection(degToRad(angle_deg), 0); sample k takes
+ * draws first_draw + 2k and first_draw + 2k + 1 of the default-state pcg32 (the reference's own stream: the test's
+ * j-th run of n samples starts at first_draw = 2 n j) and contributes the luminance of bsdf_sample's weight. albedo
+ * (3 floats, or NULL for bsdf->albedo) as in nh_bsdf_query. Needs no uploaded scene. */
+int nh_ttest_bsdf(nh_ctx *ctx, const nh_bsdf *bsdf, const float *albedo, float angle_deg, uint64_t first_draw,
+                  int32_t n, double *mean, double *variance, float *luminance);
+/* StudentsTTest::execute on device `device`: every <scene> of the file loaded, built, uploaded and run through
+ * nh_ttest_scene with the file's sampleCount (scene tests), or every <bsdf> x angle through nh_ttest_bsdf with
+ * first_draw running on across the tests (BSDF tests), then nh_students_t_test with num_tests = the number of
+ * references. Writes min(*n_results, cap) results. A chi2test file returns NH_ERR_UNSUPPORTED. Errors are reported
+ * through nh_host_last_error. */
+typedef struct nh_test_result {
+    double mean, variance, reference, p_value;
+    int32_t accepted;
+    int32_t sample_count;
+    float angle;                  /* BSDF tests: the incidence angle (degrees) */
+    int32_t pad;
+} nh_test_result;
+int nh_test_run(int device, const char *path, uint64_t seed, nh_test_result *results, int32_t cap,
+                int32_t *n_results);
 const char *nh_last_error(const nh_ctx *ctx);
 
 #ifdef __cplusplus

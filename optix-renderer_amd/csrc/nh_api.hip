@@ -18,6 +18,26 @@
 
 using nhd::DBsdf;
 
+int query_bsdf_record(nh_ctx *c, std::vector<void *> &owner, const nh_bsdf *b, const float *albedo, DBsdf &o,
+                      float alb[3]) {
+    std::memset(&o, 0, sizeof(o));
+    o.type = b->type;
+    o.ar = b->albedo[0]; o.ag = b->albedo[1]; o.ab = b->albedo[2];
+    o.alpha = b->alpha; o.int_ior = b->int_ior; o.ext_ior = b->ext_ior; o.ks = b->ks;
+    o.kr = b->kd[0]; o.kg = b->kd[1]; o.kb = b->kd[2];
+    // no texture table here: tex only selects a Disney BSDF's per-query route (albedo stands in for the lookup)
+    o.tex = b->type == NH_BSDF_DISNEY && b->albedo_texture ? 1 : 0;
+    for (int k = 0; k < 3; ++k) alb[k] = albedo ? albedo[k] : b->albedo[k];
+    if (b->type == NH_BSDF_DISNEY) {
+        nhd::DDisney *rec = nullptr;
+        const std::vector<nhd::DDisney> recs{disney_record(*b)};
+        const std::vector<float> a(alb, alb + 3);
+        if (int rc = disney_upload(c, owner, recs, a, &rec)) return rc;
+        disney_set_record(o, rec);
+    }
+    return NH_OK;
+}
+
 extern "C" {
 
 const char *nh_last_error(const nh_ctx *ctx) { return ctx ? ctx->err.c_str() : "null context"; }
@@ -146,21 +166,7 @@ int nh_bsdf_query(nh_ctx *c, const nh_bsdf *b, const float *albedo, int32_t mode
     } guard{bufs};
     nh_disney::nh::BsdfQuery q;
     std::memset(&q, 0, sizeof(q));
-    DBsdf &o = q.bsdf;
-    o.type = b->type;
-    o.ar = b->albedo[0]; o.ag = b->albedo[1]; o.ab = b->albedo[2];
-    o.alpha = b->alpha; o.int_ior = b->int_ior; o.ext_ior = b->ext_ior; o.ks = b->ks;
-    o.kr = b->kd[0]; o.kg = b->kd[1]; o.kb = b->kd[2];
-    // no texture table here: tex only selects a Disney BSDF's per-query route (albedo stands in for the lookup)
-    o.tex = b->type == NH_BSDF_DISNEY && b->albedo_texture ? 1 : 0;
-    for (int k = 0; k < 3; ++k) q.albedo[k] = albedo ? albedo[k] : b->albedo[k];
-    if (b->type == NH_BSDF_DISNEY) {
-        nhd::DDisney *rec = nullptr;
-        const std::vector<nhd::DDisney> recs{disney_record(*b)};
-        const std::vector<float> alb(q.albedo, q.albedo + 3);
-        if (int rc = disney_upload(c, bufs, recs, alb, &rec)) return rc;
-        disney_set_record(o, rec);
-    }
+    if (int rc = query_bsdf_record(c, bufs, b, albedo, q.bsdf, q.albedo)) return rc;
     q.mode = mode;
     q.n = n;
     const size_t sn = (size_t)n;

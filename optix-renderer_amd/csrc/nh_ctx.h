@@ -220,6 +220,11 @@ void disney_set_record(nhd::DBsdf &o, const nhd::DDisney *rec);
 int disney_upload(nh_ctx *c, std::vector<void *> &owner, const std::vector<nhd::DDisney> &recs,
                   const std::vector<float> &albedo, nhd::DDisney **out);
 
+// nh_api.hip: the device record of one nh_bsdf outside a scene, for nh_bsdf_query and nh_ttest_bsdf. alb: `albedo`, or
+// the BSDF's own when null; a Disney BSDF's side record is uploaded into `owner`
+int query_bsdf_record(nh_ctx *c, std::vector<void *> &owner, const nh_bsdf *b, const float *albedo, nhd::DBsdf &o,
+                      float alb[3]);
+
 inline bool fail(nh_ctx *c, const std::string &m) {
     if (c) c->err = m;
     return false;

@@ -363,3 +363,40 @@ void launch_adaptive_put(const AdaptiveLaunch &A, hipStream_t st);
 void launch_adaptive_merge(const AdaptiveLaunch &A, hipStream_t st);
 }  // namespace nh
 }  // namespace nh_disney
+
+// ---- the per-path radiance query and the t-test estimators (nh_query.hip, driven by nh_query_api.hip) ----
+// One camera path per lane, for nh_radiance_query (lum == null: entry i = sample sample[i] of pixel pixel[i];
+// pixel_sample / jitter may be null) and for the scene branch of StudentsTTest (lum != null: entry j = sample
+// first + j of pixel 0 through (a W, b H), its luminance into lum[j]; the arrays are not read)
+struct PathQuery {
+    uint64_t seed;
+    int n;
+    const int *pixel, *sample;
+    const float2 *pixel_sample;
+    float4 *rad;   // (r, g, b, -)
+    float2 *jitter;
+    uint64_t first;
+    float *lum;
+};
+// The BSDF branch of StudentsTTest: sample j takes draws first_draw + 2j, + 2j + 1 of the default-state pcg32
+struct BsdfTtest {
+    uint64_t first_draw;
+    int n;
+    nhd::DBsdf bsdf;
+    float albedo[3], wi[3];
+    float *lum;
+};
+constexpr int kTtBlock = 256;      // lanes of a reduction workgroup
+constexpr int kTtPerBlock = 4096;  // samples one workgroup reduces: the partial count depends on n alone
+namespace nh_disney {
+namespace nh {
+// built with every BSDF and emitter type; closest hits nearer child first
+void launch_path_query(const nhd::DScene *S, const nhd::Traversal &tv, const PathQuery &q, int depth, hipStream_t st);
+void launch_ttest_bsdf(const BsdfTtest &t, hipStream_t st);
+// fp64 sum over j < n of lum[j] (center == null) or (lum[j] - *center)^2, divided by `divisor`, into *out: per-lane
+// strided sums, wave shuffles, one partial per workgroup of kTtPerBlock samples (partial: (n + kTtPerBlock - 1) /
+// kTtPerBlock doubles), then one wave over the partials in index order. No atomics: the same n gives the same bits.
+void launch_ttest_reduce(const float *lum, int n, const double *center, double divisor, double *partial, double *out,
+                         hipStream_t st);
+}  // namespace nh
+}  // namespace nh_disney

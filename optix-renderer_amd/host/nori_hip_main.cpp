@@ -5,9 +5,15 @@
 // (Bitmap::save, bitmap.cpp:82-110). A scene with the adaptive sampler also prints "Total Samples Placed" and writes
 // <scene>_variance.exr (render.cpp:373, :392-413).
 //
-//   nori_hip scene.xml [--spp N] [--width W --height H] [--device D] [--ordered] [--pfm out.pfm] [--png]
-// --png also writes <scene>.png as Bitmap::saveToLDR (bitmap.cpp:122-140; the reference's hdrToLdr).
+//   nori_hip scene.xml [--spp N] [--width W --height H] [--device D] [--ordered] [--pfm out.pfm] [--png] [--seed S]
+// --png also writes <scene>.png as Bitmap::saveToLDR (bitmap.cpp:122-140; the reference's hdrToLdr). --seed: the base
+// of the per-path streams (default 0).
+// A file whose root is a <test type="ttest"> runs the reference's t-tests instead (StudentsTTest::execute,
+// src/utils/ttest.cpp): per test the sample mean, variance, t-statistic and verdict, then "Passed p/t tests."; the
+// exit status is 0 only if all passed.
+#include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -21,14 +27,43 @@ static int die(const char *what, const char *msg) {
     return 1;
 }
 
+// StudentsTTest::execute's report (ttest.cpp:163-241, hypothesis.h:324-342) for a <test> file run on the HIP path
+// (nh_test_run); 0 only if every test passed
+static int run_tests(const std::string &path, const nh_test *test, int device, unsigned long long seed) {
+    nh_test_desc td;
+    nh_test_get_desc(test, &td);
+    const size_t n_tests = td.n_bsdfs ? (size_t)td.n_bsdfs * td.n_references : td.n_scenes;
+    std::vector<nh_test_result> res(n_tests ? n_tests : 1);
+    int32_t n = 0;
+    if (nh_test_run(device, path.c_str(), seed, res.data(), (int32_t)res.size(), &n)) return die("test", nh_host_last_error());
+    const double level = 1.0 - std::pow(1.0 - (double)td.significance_level, 1.0 / (double)td.n_references);
+    int passed = 0;
+    for (int i = 0; i < n && i < (int)res.size(); ++i) {
+        const nh_test_result &r = res[i];
+        std::printf("------------------------------------------------------\n");
+        if (td.n_bsdfs) std::printf("Testing (angle=%g): BSDF %d\nDrawing %d samples .. \n", r.angle, i / (int)td.n_references, r.sample_count);
+        else std::printf("Testing scene: %d\nGenerating %d paths.. \n", i, r.sample_count);
+        const double t = std::fabs(r.mean - r.reference) * std::sqrt(r.sample_count / std::max(r.variance, 1e-5));
+        std::printf("Sample mean = %g (reference value = %g)\n", r.mean, r.reference);
+        std::printf("Sample variance = %g\n", r.variance);
+        std::printf("t-statistic = %g (d.o.f. = %d)\n", t, r.sample_count - 1);
+        std::printf("%s the null hypothesis (p-value = %g, significance level = %g)\n\n",
+                    r.accepted ? "Accepted" : "***** Rejected *****", r.p_value, level);
+        passed += r.accepted ? 1 : 0;
+    }
+    std::printf("Passed %d/%d tests.\n", passed, (int)n);
+    return passed == n ? 0 : 1;
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) {
-        std::fprintf(stderr, "usage: nori_hip scene.xml [--spp N] [--width W --height H] [--device D] [--ordered] [--pfm out] [--png]\n");
+        std::fprintf(stderr, "usage: nori_hip scene.xml [--spp N] [--width W --height H] [--device D] [--ordered] [--pfm out] [--png] [--seed S]\n");
         return 1;
     }
     std::string scene_path = argv[1], pfm;
     bool png = false;
     int spp = 0, w = 0, h = 0, device = 0, traversal = NH_TRAVERSAL_REFERENCE;
+    unsigned long long seed = 0;
     for (int i = 2; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() { return i + 1 < argc ? argv[++i] : (char *)"0"; };
@@ -39,8 +74,18 @@ int main(int argc, char **argv) {
         else if (a == "--ordered") traversal = NH_TRAVERSAL_ORDERED;
         else if (a == "--pfm") pfm = next();
         else if (a == "--png") png = true;
+        else if (a == "--seed") seed = std::strtoull(next(), nullptr, 0);
         else return die("argument", a.c_str());
     }
+    // a <test> root runs the reference's t-tests (StudentsTTest::execute) instead of a render
+    nh_test *test = nullptr;
+    const int trc = nh_test_load_xml(scene_path.c_str(), &test);
+    if (trc == NH_OK) {
+        const int rc = run_tests(scene_path, test, device, seed);
+        nh_test_free(test);
+        return rc;
+    }
+    if (trc != NH_ERR_INVALID) return die("load", nh_host_last_error());  // (NH_ERR_INVALID: not a <test> root)
     nh_scene *scene = nullptr;
     if (nh_scene_load_xml(scene_path.c_str(), &scene)) return die("load", nh_host_last_error());
     if (w > 0 && h > 0) nh_scene_set_resolution(scene, w, h);
@@ -60,6 +105,7 @@ int main(int argc, char **argv) {
     std::memset(&req, 0, sizeof(req));
     req.sample_begin = 0;
     req.sample_end = desc.sample_count;
+    req.seed = seed;
     req.mode = NH_MODE_MEGAKERNEL;
     req.traversal = traversal;
     req.clear = 1;

@@ -1185,9 +1185,7 @@ void build_scene(const Obj &scene, const std::string &base_dir, SceneData &sd) {
     camera_update(sd);
 }
 
-}  // namespace
-
-SceneData *load_scene(const std::string &path, int scene_index) {
+std::unique_ptr<Obj> parse_file(const std::string &path) {
     std::ifstream is(path, std::ios::binary);
     if (is.fail()) throw SceneError("unable to open scene file \"" + path + "\"");
     std::stringstream ss;
@@ -1200,7 +1198,95 @@ SceneData *load_scene(const std::string &path, int scene_index) {
         throw SceneError("Error while parsing \"" + path + "\": " + e.what());
     }
     ParseCtx c{text, path};
-    auto obj = parse_node(*root, nullptr, "", c);
+    return parse_node(*root, nullptr, "", c);
+}
+
+std::string dir_of(const std::string &path) {
+    auto slash = path.find_last_of('/');
+    return slash != std::string::npos ? path.substr(0, slash) : std::string();
+}
+
+// classTypeName (include/nori/object.h:63-104) of the object a tag creates
+const char *class_type_name(const std::string &tag) {
+    static const char *const names[][2] = {
+        {"scene", "EScene"}, {"shape", "EShape"}, {"texture", "ETexture"}, {"volume", "EVolume"}, {"bsdf", "EBSDF"},
+        {"phase", "EPhaseFunction"}, {"emitter", "EEmitter"}, {"medium", "EMedium"}, {"camera", "ECamera"},
+        {"integrator", "EIntegrator"}, {"sampler", "ESampler"}, {"pxsampler", "EPixelSampler"},
+        {"denoiser", "EDenoiser"}, {"test", "ETest"}, {"rfilter", "EReconstructionFilter"}, {"renderer", "ERenderer"}};
+    for (auto &n : names)
+        if (tag == n[0]) return n[1];
+    return "<unknown>";
+}
+
+// a list property of a <test>: tokenize(propList.getString(name, "")) then toFloat (ttest.cpp:68-75). The XML parser
+// of the reference turns the tabs and line breaks of an attribute value into spaces before that. As there, an absent
+// or empty list is one empty token, and toFloat (common.cpp:105-112) reads an empty token as 0: the list {0}.
+std::vector<float> float_list(const PropList &p, const char *name) {
+    std::string s = p.get_string(name, "");
+    for (char &ch : s)
+        if (ch == '\t' || ch == '\n' || ch == '\r') ch = ' ';
+    std::vector<float> out;
+    for (const std::string &t : tokenize(s)) {
+        char *end = nullptr;
+        const float v = std::strtof(t.c_str(), &end);
+        if (*end != '\0') throw SceneError("Could not parse floating point value \"" + t + "\"");
+        out.push_back(v);
+    }
+    return out;
+}
+
+}  // namespace
+
+// A <test> root (src/utils/ttest.cpp, chi2test.cpp): the constructor's properties and the children StudentsTTest
+// keeps, with addChild's and execute()'s errors. The <scene> children are counted, not built (load_scene builds one).
+struct NotATest : SceneError {
+    using SceneError::SceneError;
+};
+struct TestData {
+    int32_t type = NH_TEST_TTEST;
+    float significance_level = 0.01f;
+    int32_t sample_count = 0;
+    std::vector<float> angles, references;
+    uint32_t n_scenes = 0;
+    std::vector<nh_bsdf> bsdfs;
+};
+
+TestData *load_test(const std::string &path) {
+    auto obj = parse_file(path);
+    if (obj->tag != "test") throw NotATest("root element <" + obj->tag + "> is not a test");
+    auto td = std::make_unique<TestData>();
+    const PropList &p = obj->props;
+    const bool chi2 = obj->type == "chi2test";
+    if (!chi2 && obj->type != "ttest") throw SceneError("test type \"" + obj->type + "\" is not supported by the HIP path");
+    td->type = chi2 ? NH_TEST_CHI2TEST : NH_TEST_TTEST;
+    td->significance_level = p.get_float("significanceLevel", 0.01f);
+    td->sample_count = p.get_int("sampleCount", chi2 ? -1 : 100000);
+    if (!chi2) {
+        td->angles = float_list(p, "angles");
+        td->references = float_list(p, "references");
+    }
+    SceneData scratch;  // the BSDF parser appends a textured BSDF's textures to a scene
+    for (auto &ch : obj->children) {
+        if (ch->tag == "bsdf") td->bsdfs.push_back(make_bsdf(*ch, dir_of(path), scratch));
+        else if (ch->tag == "scene" && !chi2) td->n_scenes++;
+        else
+            throw SceneError(std::string(chi2 ? "ChiSquareTest" : "StudentsTTest") + "::addChild(<" +
+                             class_type_name(ch->tag) + ">) is not supported!");
+    }
+    if (!chi2) {  // StudentsTTest::execute (ttest.cpp:151-155, :192-193)
+        if (!td->bsdfs.empty()) {
+            if (td->references.size() * td->bsdfs.size() != td->angles.size())
+                throw SceneError("Specified a different number of angles and reference values!");
+            if (td->n_scenes) throw SceneError("Cannot test BSDFs and scenes at the same time!");
+        } else if (td->references.size() != td->n_scenes) {
+            throw SceneError("Specified a different number of scenes and reference values!");
+        }
+    }
+    return td.release();
+}
+
+SceneData *load_scene(const std::string &path, int scene_index) {
+    auto obj = parse_file(path);
     const Obj *scene = nullptr;
     if (obj->tag == "scene") {
         if (scene_index > 0) throw SceneError("scene index out of range");
@@ -1293,6 +1379,47 @@ static int load_impl(const char *path, int index, nh_scene **out) {
 
 int nh_scene_load_xml(const char *path, nh_scene **out) { return load_impl(path, 0, out); }
 int nh_scene_load_xml_index(const char *path, int32_t index, nh_scene **out) { return load_impl(path, index, out); }
+
+struct nh_test {
+    nh::TestData *data;
+};
+
+int nh_test_load_xml(const char *path, nh_test **out) {
+    if (!path || !out) { nh::set_host_error("null argument"); return NH_ERR_INVALID; }
+    try {
+        *out = new nh_test{nh::load_test(path)};
+        return NH_OK;
+    } catch (const nh::NotATest &e) {
+        nh::set_host_error(e.what());
+        return NH_ERR_INVALID;
+    } catch (const std::exception &e) {
+        nh::set_host_error(e.what());
+        return NH_ERR_IO;
+    }
+}
+
+int nh_test_get_desc(const nh_test *test, nh_test_desc *out) {
+    if (!test || !out) { nh::set_host_error("null argument"); return NH_ERR_INVALID; }
+    const nh::TestData &t = *test->data;
+    std::memset(out, 0, sizeof(*out));
+    out->type = t.type;
+    out->significance_level = t.significance_level;
+    out->sample_count = t.sample_count;
+    out->n_angles = (uint32_t)t.angles.size();
+    out->angles = t.angles.data();
+    out->n_references = (uint32_t)t.references.size();
+    out->references = t.references.data();
+    out->n_scenes = t.n_scenes;
+    out->n_bsdfs = (uint32_t)t.bsdfs.size();
+    out->bsdfs = t.bsdfs.data();
+    return NH_OK;
+}
+
+void nh_test_free(nh_test *test) {
+    if (!test) return;
+    delete test->data;
+    delete test;
+}
 
 int nh_scene_get_desc(const nh_scene *scene, nh_scene_desc *out) {
     if (!scene || !out) { nh::set_host_error("null argument"); return NH_ERR_INVALID; }

@@ -261,6 +261,31 @@ _sig("nh_emitter_query", _i32, _vp, _u32, _i32, _i32, _fp, _fp, _fp)
 _sig("nh_medium_query", _i32, _vp, _u32, _i32, _i32, _fp, _fp)
 _sig("nh_last_error", C.c_char_p, _vp)
 
+
+class nh_test_desc(C.Structure):
+    _fields_ = [("type", _i32), ("significance_level", _f), ("sample_count", _i32), ("n_angles", _u32),
+                ("angles", _fp), ("n_references", _u32), ("references", _fp), ("n_scenes", _u32), ("n_bsdfs", _u32),
+                ("bsdfs", C.POINTER(nh_bsdf))]
+
+
+class nh_test_result(C.Structure):
+    _fields_ = [("mean", C.c_double), ("variance", C.c_double), ("reference", C.c_double), ("p_value", C.c_double),
+                ("accepted", _i32), ("sample_count", _i32), ("angle", _f), ("pad", _i32)]
+
+
+TEST_TTEST, TEST_CHI2TEST = 0, 1
+RADIANCE_QUERY_MAX = 1 << 24  # NH_RADIANCE_QUERY_MAX
+_dp = C.POINTER(C.c_double)
+_i32p = C.POINTER(_i32)
+_sig("nh_test_load_xml", _i32, C.c_char_p, C.POINTER(_vp))
+_sig("nh_test_get_desc", _i32, _vp, C.POINTER(nh_test_desc))
+_sig("nh_test_free", None, _vp)
+_sig("nh_students_t_test", _i32, C.c_double, C.c_double, C.c_double, _i32, C.c_double, _i32, _i32p, _dp)
+_sig("nh_radiance_query", _i32, _vp, C.c_uint64, _i32, _i32p, _i32p, _fp, _fp, _fp)
+_sig("nh_ttest_scene", _i32, _vp, C.c_uint64, C.c_int64, _i32, _dp, _dp, _fp)
+_sig("nh_ttest_bsdf", _i32, _vp, C.POINTER(nh_bsdf), _fp, _f, C.c_uint64, _i32, _dp, _dp, _fp)
+_sig("nh_test_run", _i32, C.c_int, C.c_char_p, C.c_uint64, C.POINTER(nh_test_result), _i32, _i32p)
+
 lib = _lib
 _hip_used = False  # set by the first call that initialises the HIP runtime (device_count, Context)
 
@@ -416,6 +441,58 @@ class Scene:
         d = self.desc
         b = d.filter.border
         return (d.camera.height + 2 * b, d.camera.width + 2 * b, 4)
+
+
+class Test:
+    """A loaded <test> root (nh_test_load_xml): StudentsTTest's or ChiSquareTest's properties and children. Loading
+    raises NoriError with the reference's own message where StudentsTTest's addChild or execute() throw."""
+    __test__ = False  # (not a pytest class)
+
+    def __init__(self, path: str):
+        h = _vp()
+        _host_check(_lib.nh_test_load_xml(path.encode(), C.byref(h)), f"load {path}")
+        self._h = h
+        self.path = path
+        d = nh_test_desc()
+        _host_check(_lib.nh_test_get_desc(h, C.byref(d)), "test_get_desc")
+        self.type = "chi2test" if d.type == TEST_CHI2TEST else "ttest"
+        self.significance_level = np.float32(d.significance_level)
+        self.sample_count = int(d.sample_count)
+        self.angles = [np.float32(d.angles[i]) for i in range(d.n_angles)]
+        self.references = [np.float32(d.references[i]) for i in range(d.n_references)]
+        self.n_scenes = int(d.n_scenes)
+        self.bsdfs = []
+        for i in range(d.n_bsdfs):  # copies: the handle owns the originals
+            b = nh_bsdf()
+            C.memmove(C.byref(b), C.byref(d.bsdfs[i]), C.sizeof(nh_bsdf))
+            self.bsdfs.append(b)
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            _lib.nh_test_free(self._h)
+            self._h = None
+
+
+def students_t_test(mean: float, variance: float, reference: float, n: int, alpha: float, num_tests: int):
+    """hypothesis::students_t_test (nh_students_t_test): (accepted, two-sided p-value) at the Sidak-corrected level."""
+    ok, p = _i32(0), C.c_double(0.0)
+    _host_check(_lib.nh_students_t_test(mean, variance, reference, n, alpha, num_tests, C.byref(ok), C.byref(p)),
+                "students_t_test")
+    return bool(ok.value), p.value
+
+
+def run_tests(path: str, seed: int = 0, device: int = 0) -> list:
+    """StudentsTTest::execute on the HIP path (nh_test_run): one dict per test of the file -- mean, variance,
+    reference, p_value, accepted, sample_count, angle (BSDF tests)."""
+    global _hip_used
+    _hip_used = True
+    t = Test(path)
+    cap = max(1, t.n_scenes + len(t.bsdfs) * len(t.references))
+    n = _i32(0)
+    res = (nh_test_result * cap)()
+    _host_check(_lib.nh_test_run(device, path.encode(), seed, res, cap, C.byref(n)), f"run_tests {path}")
+    return [{"mean": r.mean, "variance": r.variance, "reference": r.reference, "p_value": r.p_value,
+             "accepted": bool(r.accepted), "sample_count": r.sample_count, "angle": r.angle} for r in res[:n.value]]
 
 
 def texture_decode(rgba8, srgb: bool) -> np.ndarray:
@@ -638,6 +715,41 @@ class Context:
         out = np.zeros((len(inp), n_out), np.float32)
         self._check(_lib.nh_medium_query(self._h, medium, mode, len(inp), _fptr(inp), _fptr(out)), "medium_query")
         return out[:, 0] if n_out == 1 else out
+
+    def radiance_query(self, pixel, sample, seed: int = 0, pixel_sample=None) -> dict:
+        """nh_radiance_query: the radiance of sample sample[i] of pixel pixel[i] (y * width + x) of the uploaded scene
+        under `seed`, by the render kernels' own integrators, unfiltered. pixel_sample (n, 2): the image-plane
+        positions to shoot through instead of pixel + jitter. {"rgb": (n, 3), "jitter": (n, 2)} float32."""
+        pixel = np.ascontiguousarray(pixel, dtype=np.int32).ravel()
+        sample = np.ascontiguousarray(np.broadcast_to(np.asarray(sample, dtype=np.int32), pixel.shape))
+        n = len(pixel)
+        ps = None if pixel_sample is None else np.ascontiguousarray(pixel_sample, dtype=np.float32).reshape(n, 2)
+        out = {"rgb": np.zeros((n, 3), np.float32), "jitter": np.zeros((n, 2), np.float32)}
+        self._check(_lib.nh_radiance_query(self._h, seed, n, pixel.ctypes.data_as(_i32p), sample.ctypes.data_as(_i32p),
+                                           None if ps is None else _fptr(ps), _fptr(out["rgb"]), _fptr(out["jitter"])),
+                    "radiance_query")
+        return out
+
+    def ttest_scene(self, n: int, seed: int = 0, first: int = 0, luminance: bool = False):
+        """nh_ttest_scene: StudentsTTest's scene estimator over samples first .. first + n - 1 of the uploaded scene,
+        each on its own stream (seed, pixel 0, sample k). (mean, variance), and the n luminances (float32) as a third
+        element with luminance=True."""
+        m, v = C.c_double(0.0), C.c_double(0.0)
+        lum = np.zeros(max(n, 0), np.float32) if luminance else None
+        self._check(_lib.nh_ttest_scene(self._h, seed, first, n, C.byref(m), C.byref(v),
+                                        None if lum is None else _fptr(lum)), "ttest_scene")
+        return (m.value, v.value, lum) if luminance else (m.value, v.value)
+
+    def ttest_bsdf(self, bsdf: nh_bsdf, angle_deg: float, n: int, first_draw: int = 0, albedo=None,
+                   luminance: bool = False):
+        """nh_ttest_bsdf: StudentsTTest's BSDF estimator at incidence angle angle_deg: sample k takes draws
+        first_draw + 2k, + 2k + 1 of the default-state pcg32. Returns as ttest_scene."""
+        m, v = C.c_double(0.0), C.c_double(0.0)
+        lum = np.zeros(max(n, 0), np.float32) if luminance else None
+        alb = None if albedo is None else np.ascontiguousarray(albedo, dtype=np.float32).reshape(3)
+        self._check(_lib.nh_ttest_bsdf(self._h, C.byref(bsdf), None if alb is None else _fptr(alb), angle_deg, first_draw,
+                                       n, C.byref(m), C.byref(v), None if lum is None else _fptr(lum)), "ttest_bsdf")
+        return (m.value, v.value, lum) if luminance else (m.value, v.value)
 
     def trace(self, o: np.ndarray, d: np.ndarray, mint: np.ndarray, maxt: np.ndarray, any_hit=False,
               traversal: int = TRAVERSAL_REFERENCE) -> dict:
