@@ -21,9 +21,11 @@ HIP_FLAGS  := -std=c++17 -O3 -fPIC --offload-arch=$(ARCH) $(FP_FLAGS) \
               -Iinclude -I$(PKG)/csrc -Wno-unused-result $(EXTRA_HIP)
 
 HOST_SRC := $(PKG)/host/xml_lite.cpp $(PKG)/host/scene_loader.cpp $(PKG)/host/bvh_build.cpp $(PKG)/host/image_io.cpp \
-            $(PKG)/host/png_decode.cpp $(PKG)/host/hdr_decode.cpp $(PKG)/host/gpu_layout.cpp $(PKG)/host/ttest.cpp
+            $(PKG)/host/png_decode.cpp $(PKG)/host/hdr_decode.cpp $(PKG)/host/gpu_layout.cpp $(PKG)/host/ttest.cpp \
+            $(PKG)/host/photon_host.cpp
 HIP_SRC  := $(PKG)/csrc/nh_kernels.hip $(PKG)/csrc/nh_denoise.hip $(PKG)/csrc/nh_splat.hip $(PKG)/csrc/nh_api.hip \
-            $(PKG)/csrc/nh_upload.hip $(PKG)/csrc/nh_pipeline.hip $(PKG)/csrc/nh_adaptive_api.hip $(PKG)/csrc/nh_query_api.hip
+            $(PKG)/csrc/nh_upload.hip $(PKG)/csrc/nh_pipeline.hip $(PKG)/csrc/nh_adaptive_api.hip $(PKG)/csrc/nh_query_api.hip \
+            $(PKG)/csrc/nh_photon_api.hip
 HOST_OBJ := $(patsubst $(PKG)/host/%.cpp,$(OBJDIR)/host_%.o,$(HOST_SRC))
 # nh_wavefront.hip is compiled as five translation units (-DNH_WF_PART=k, each instantiating its own kernels) so
 # its kernels build in parallel
@@ -37,11 +39,12 @@ HIP_OBJ  := $(patsubst $(PKG)/csrc/%.hip,$(OBJDIR)/hip_%.o,$(HIP_SRC)) \
 # part 4 (the diffuse area-light instantiations) have no variant, and parts 1 and 2 leave their other kernels out.
 # nh_volume.hip (the volumetric path tracers and the medium query) is built this way only: one copy, with every BSDF
 # and emitter type. So are nh_adaptive.hip (the adaptive sampler's kernels) and nh_query.hip (the radiance query and the
-# t-test estimators). The integrators themselves are device
+# t-test estimators) and nh_photon.hip (the photon mapper's passes). The integrators themselves are device
 # function templates in headers (nh_integrators.h, nh_volume.h), shared by these units.
 DZ_PARTS := 1 2
 HIP_OBJ  += $(OBJDIR)/hipdz_nh_kernels.o $(OBJDIR)/hipdz_nh_disney.o $(OBJDIR)/hipdz_nh_emitter_query.o \
             $(OBJDIR)/hipdz_nh_volume.o $(OBJDIR)/hipdz_nh_adaptive.o $(OBJDIR)/hipdz_nh_query.o \
+            $(OBJDIR)/hipdz_nh_photon.o \
             $(foreach k,$(DZ_PARTS),$(OBJDIR)/hipdz_nh_wavefront_p$(k).o)
 HIP_DEPS := $(wildcard $(PKG)/csrc/*.h) $(PKG)/host/gpu_layout.h include/nori_hip.h
 # The wavefront kernels build without LLVM's machine-level LICM: it hoists loop invariants out of the traversal, bounce

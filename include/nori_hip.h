@@ -65,7 +65,9 @@ enum { NH_INTEGRATOR_PATH_MIS = 0, NH_INTEGRATOR_PATH_MATS = 1, NH_INTEGRATOR_DI
        NH_INTEGRATOR_NORMALS = 6,
        /* the volumetric path tracers (path_vol_mats.cpp, path_vol_mis.cpp): the only integrators that render a scene
           with a participating medium or a shape without a BSDF */
-       NH_INTEGRATOR_PATH_VOL_MATS = 7, NH_INTEGRATOR_PATH_VOL_MIS = 8 };
+       NH_INTEGRATOR_PATH_VOL_MATS = 7, NH_INTEGRATOR_PATH_VOL_MIS = 8,
+       /* the photon mapper (photonmapper.cpp): renders once nh_photon_map_build has built the context's photon map */
+       NH_INTEGRATOR_PHOTONMAPPER = 9 };
 
 /* One Nori Shape (src/shapes/mesh.cpp, src/shapes/sphere.cpp). Mesh data lives in
  * the scene-wide concatenated arrays at the given offsets. */
@@ -449,6 +451,21 @@ int nh_scene_set_lens_draw_order(nh_scene *scene, int32_t order);
    reference's behaviour, reproduced). out: n floats. */
 int nh_texture_decode(const uint8_t *rgba8, uint64_t n, int32_t srgb, float *out);
 int nh_scene_set_integrator(nh_scene *scene, int32_t integrator);
+/* <integrator type="photonmapper"> (src/integrators/photonmapper.cpp:36-41): photonCount [1000000] and photonRadius
+ * [0 = automatic]. Kept beside nh_scene_desc, which does not grow. nh_scene_get_photon_params returns the radius
+ * resolved as PhotonMapper::preprocess does (photonmapper.cpp:75-76): a radius of 0 becomes
+ * scene->getBoundingBox().getExtents().norm() / 500.0f, in fp32 with Eigen's grouping, over the union of the shapes'
+ * boxes (the BVH root box). nh_scene_set_photon_params overrides both (photon_count >= 1, photon_radius >= 0 and
+ * finite; 0 = automatic again). On a scene with another integrator get returns the defaults. */
+typedef struct nh_photon_params {
+    int32_t photon_count;
+    float photon_radius;
+} nh_photon_params;
+int nh_scene_get_photon_params(const nh_scene *scene, nh_photon_params *out);
+int nh_scene_set_photon_params(nh_scene *scene, const nh_photon_params *params);
+/* PhotonData::initialize (src/utils/photon.cpp:30-41): the five 256-entry decode tables, built with std::cos /
+ * std::sin / std::ldexp on float as there; exp_table[0] = 0. Host only. */
+int nh_photon_tables(float *cos_theta, float *sin_theta, float *cos_phi, float *sin_phi, float *exp_table);
 void nh_scene_free(nh_scene *scene);
 const char *nh_host_last_error(void);
 /* Parity hook for the loader's transform arithmetic (the Eigen operations of parser.cpp:308-360,
@@ -549,8 +566,15 @@ int nh_bsdf_query(nh_ctx *ctx, const nh_bsdf *bsdf, const float *albedo, int32_t
  *   NH_EMITTER_QUERY_PDF         [3..5] the point p on the light, [6..8] its normal n (p and n are read for area
  *                                lights only). out: 3 floats per query (eval's value), 1 float per query (pdf)
  * Needs an uploaded scene (nh_upload_scene; no BVH). */
-enum { NH_EMITTER_QUERY_SAMPLE = 0, NH_EMITTER_QUERY_EVAL = 1, NH_EMITTER_QUERY_PDF = 2 };
+enum { NH_EMITTER_QUERY_SAMPLE = 0, NH_EMITTER_QUERY_EVAL = 1, NH_EMITTER_QUERY_PDF = 2,
+       /* Emitter::samplePhoton of an area light (arealight.cpp:127-144), by the device function the photon pass calls.
+          in: sample = 4n floats (sample1.x, sample1.y, sample2.x, sample2.y); ref is not read (may be NULL). out:
+          NH_EMITTER_QUERY_PHOTON_STRIDE floats per query: [0..2] the ray's origin, [3..5] its direction, [6..8] W =
+          M_PI / pdf * radiance * the number of emitters (photonmapper.cpp:91), [9] the surface pdf, [10..11] 0.
+          NH_ERR_UNSUPPORTED for an emitter that is not an area light. */
+       NH_EMITTER_QUERY_SAMPLE_PHOTON = 3 };
 #define NH_EMITTER_QUERY_SAMPLE_STRIDE 16
+#define NH_EMITTER_QUERY_PHOTON_STRIDE 12
 #define NH_EMITTER_QUERY_IN_STRIDE 9
 int nh_emitter_query(nh_ctx *ctx, uint32_t emitter, int32_t mode, int32_t n, const float *ref, const float *sample,
                      float *out);
@@ -638,6 +662,46 @@ typedef struct nh_test_result {
 } nh_test_result;
 int nh_test_run(int device, const char *path, uint64_t seed, nh_test_result *results, int32_t cap,
                 int32_t *n_results);
+
+/* ---- the photon mapper (src/integrators/photonmapper.cpp) ------------------------------- */
+
+/* Photon path k draws from its own stream path_rng(seed, NH_PHOTON_STREAM, k): no pixel index reaches 2^32. */
+#define NH_PHOTON_STREAM ((uint64_t)1 << 32)
+/* paths of one launch of the photon pass when batch_paths = 0 */
+#define NH_PHOTON_DEFAULT_BATCH (1 << 18)
+/* PhotonMapper::preprocess on the uploaded scene and BVH: photon paths 0, 1, .. are traced (photonmapper.cpp:86-149)
+ * and deposit (its.p, -d, W) at every hit of a diffuse or Disney BSDF. The map holds the first photon_count deposits
+ * in (path, bounce) order; the emitted count E is the number of paths up to and including the one that fills it.
+ * Neither depends on batch_paths (paths per launch, 0 = NH_PHOTON_DEFAULT_BATCH) nor on anything else about how the
+ * pass is launched. params->photon_radius = 0 resolves as nh_scene_get_photon_params does, from the uploaded BVH's
+ * root box. The map lives in the context until the next build or scene / BVH upload; nh_render, nh_radiance_query
+ * and nh_ttest_scene of a photon-mapper scene return NH_ERR_STATE without one. NH_ERR_UNSUPPORTED: the scene's
+ * integrator is not the photon mapper, an emitter is not an area light, the first 2^16 paths deposit nothing ("no
+ * photon reaches a diffuse surface": the reference would loop forever), or E would pass INT32_MAX. */
+int nh_photon_map_build(nh_ctx *ctx, const nh_photon_params *params, uint64_t seed, int32_t batch_paths);
+typedef struct nh_photon_stats {
+    int32_t stored;               /* photons in the map (= photon_count) */
+    int32_t emitted;              /* E, m_emittedPhotons */
+    float radius;                 /* the resolved gather radius */
+    float cell_size;              /* side of a cell of the search grid (>= radius) */
+    uint64_t occupied_cells;      /* grid cells that hold a photon */
+} nh_photon_stats;
+int nh_get_photon_stats(nh_ctx *ctx, nh_photon_stats *out);
+/* Photons first .. first + n - 1 in deposit order ((path, bounce) ascending). Every output may be NULL: position (3n
+ * floats), direction and power as the gather reads them, i.e. decoded from the stored bytes through PhotonData's
+ * tables (3n each), bytes (6n: theta, phi, rgbe[0..3]), path index and bounce (n each). */
+int nh_get_photons(nh_ctx *ctx, int32_t first, int32_t n, float *position, float *direction, float *power,
+                   uint8_t *bytes, int32_t *path, int32_t *bounce);
+/* Point queries by the device functions the photon pass and the gather call.
+ *   NH_PHOTON_QUERY_CODEC   in: 6n floats (direction, power). bytes: 6n (theta, phi, rgbe[0..3] of PhotonData's
+ *                           constructor, photon.cpp:43-74); out: 6n floats (getDirection, getPower of those bytes).
+ *                           count is not written. Needs no scene.
+ *   NH_PHOTON_QUERY_GATHER  in: 3n floats (points). count: n (photons with (photon.p - p).squaredNorm() < r * r in
+ *                           fp32); out: 3n floats (the fp32 sum of their decoded powers, added in ascending (cell key,
+ *                           deposit index) order, the order of the render's gather). bytes is not written. Needs a map. */
+enum { NH_PHOTON_QUERY_CODEC = 0, NH_PHOTON_QUERY_GATHER = 1 };
+int nh_photon_query(nh_ctx *ctx, int32_t mode, int32_t n, const float *in, uint8_t *bytes, int32_t *count, float *out);
+
 const char *nh_last_error(const nh_ctx *ctx);
 
 #ifdef __cplusplus

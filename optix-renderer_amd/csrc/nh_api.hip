@@ -84,7 +84,9 @@ void nh_destroy(nh_ctx *c) {
     (void)hipFree(c->block_rank);
     (void)hipFree(c->staging);
     (void)hipFree(c->counters);
+    photon_release(c, true);  // (clears the map's record in d_scene: before d_scene goes)
     (void)hipFree(c->d_scene);
+    c->d_scene = nullptr;
     for (WfPool &p : c->pools) pool_free(p);
     adaptive_release(c);
     c->comms.reset();  // the communicators go with the last context of their set
@@ -199,17 +201,21 @@ int nh_bsdf_query(nh_ctx *c, const nh_bsdf *b, const float *albedo, int32_t mode
 int nh_emitter_query(nh_ctx *c, uint32_t emitter, int32_t mode, int32_t n, const float *ref, const float *sample,
                      float *out) {
     if (!c) return NH_ERR_INVALID;
-    if (n < 0 || !ref || !sample || !out) return fail(c, "nh_emitter_query: null argument"), NH_ERR_INVALID;
-    if (mode < NH_EMITTER_QUERY_SAMPLE || mode > NH_EMITTER_QUERY_PDF)
+    const bool photon = mode == NH_EMITTER_QUERY_SAMPLE_PHOTON;  // reads no reference point
+    if (n < 0 || (!ref && !photon) || !sample || !out) return fail(c, "nh_emitter_query: null argument"), NH_ERR_INVALID;
+    if (mode < NH_EMITTER_QUERY_SAMPLE || mode > NH_EMITTER_QUERY_SAMPLE_PHOTON)
         return fail(c, "nh_emitter_query: unknown mode"), NH_ERR_INVALID;
     if (!c->has_scene) return fail(c, "nh_emitter_query: no scene uploaded"), NH_ERR_STATE;
     if (emitter >= c->h_emitters.size()) return fail(c, "nh_emitter_query: emitter index out of range"), NH_ERR_INVALID;
     const nhd::DEmitter &e = c->h_emitters[emitter];
     if (e.type == NH_EMITTER_AREA && (e.shape < 0 || (size_t)e.shape >= c->h_shapes.size()))
         return fail(c, "nh_emitter_query: area light without a valid shape"), NH_ERR_INVALID;
+    if (photon && e.type != NH_EMITTER_AREA)
+        return fail(c, "nh_emitter_query: samplePhoton of an emitter that is not an area light is not supported"),
+               NH_ERR_UNSUPPORTED;
     const size_t sn = (size_t)n;
-    if (mode == NH_EMITTER_QUERY_SAMPLE)  // (the CDF searches of the area and envmap samples index by it)
-        for (size_t i = 0; i < 2 * sn; ++i)
+    if (mode == NH_EMITTER_QUERY_SAMPLE || photon)  // (the CDF searches of the area and envmap samples index by it)
+        for (size_t i = 0; i < (photon ? 4 : 2) * sn; ++i)
             if (!(sample[i] >= 0.f && sample[i] < 1.f))
                 return fail(c, "nh_emitter_query: sample outside [0, 1)"), NH_ERR_INVALID;
     if (n == 0) return NH_OK;
@@ -228,10 +234,13 @@ int nh_emitter_query(nh_ctx *c, uint32_t emitter, int32_t mode, int32_t n, const
     q.emitter = (int)emitter;
     q.mode = mode;
     q.n = n;
-    const size_t in_stride = mode == NH_EMITTER_QUERY_SAMPLE ? 2 : NH_EMITTER_QUERY_IN_STRIDE;
-    const size_t out_stride = mode == NH_EMITTER_QUERY_SAMPLE ? NH_EMITTER_QUERY_SAMPLE_STRIDE
-                                                              : (mode == NH_EMITTER_QUERY_EVAL ? 3 : 1);
-    if (int rc = upload(c, bufs, ref, 3 * sn, &q.ref)) return rc;
+    const size_t in_stride = photon ? 4 : (mode == NH_EMITTER_QUERY_SAMPLE ? 2 : NH_EMITTER_QUERY_IN_STRIDE);
+    const size_t out_stride = photon ? NH_EMITTER_QUERY_PHOTON_STRIDE
+                                     : (mode == NH_EMITTER_QUERY_SAMPLE ? NH_EMITTER_QUERY_SAMPLE_STRIDE
+                                                                        : (mode == NH_EMITTER_QUERY_EVAL ? 3 : 1));
+    q.ref = nullptr;
+    if (!photon)
+        if (int rc = upload(c, bufs, ref, 3 * sn, &q.ref)) return rc;
     if (int rc = upload(c, bufs, sample, in_stride * sn, &q.in)) return rc;
     void *d_out = nullptr;
     HIP_TRY(c, hipMalloc(&d_out, out_stride * sn * sizeof(float)));

@@ -133,6 +133,20 @@ struct AdaptiveState {
     std::vector<int4> h_blocks;  // by rank
 };
 
+// The photon mapper's map (nh_photon_api.hip): lives from nh_photon_map_build to the next build or upload
+struct PhotonState {
+    bool built = false;
+    std::vector<void *> bufs;      // everything the map owns on the device
+    const float *tables = nullptr; // PhotonData's decode tables (nh_photon.h), uploaded on first use; not in bufs
+    std::vector<float> h_tables;
+    // deposit order (nh_get_photons)
+    float *pos = nullptr;
+    uint2 *bytes = nullptr;
+    uint32_t *path = nullptr;
+    int *bounce = nullptr;
+    nh_photon_stats stats{};
+};
+
 struct nh_ctx {
     uint64_t id = 0;  // unique per context (process lifetime): identifies comm-set members
     std::shared_ptr<CommSet> comms;
@@ -172,6 +186,7 @@ struct nh_ctx {
     bool bsdfless = false, has_media = false;
     int sampler = 0, adaptive_initial_uniform = 0;  // NH_SAMPLER_*; an adaptive scene renders through render_adaptive
     AdaptiveState ad;
+    PhotonState photon;
     // host copies of the scene tables and the emit_faces count, for the LDS image of a small scene (build_small_image)
     std::vector<nhd::DShape> h_shapes;
     std::vector<nhd::DBsdf> h_bsdfs;
@@ -214,6 +229,8 @@ int check_device(nh_ctx *c, const char *where);
 // every scene's is, the pipeline drained); release of its buffers (nh_destroy, and every scene upload)
 int render_adaptive(nh_ctx *c, const nh_render_req *q);
 void adaptive_release(nh_ctx *c);
+// nh_photon_api.hip: drops the context's photon map (every scene / BVH upload; nh_destroy also frees the tables)
+void photon_release(nh_ctx *c, bool tables = false);
 // nh_upload.hip: the DDisney side record of a Disney BSDF (nh_bsdf_query builds one too)
 nhd::DDisney disney_record(const nh_bsdf &b);
 void disney_set_record(nhd::DBsdf &o, const nhd::DDisney *rec);

@@ -261,6 +261,20 @@ struct alignas(16) DMedium {
     int pad[3];
 };
 static_assert(sizeof(DMedium) == 64, "medium record");
+// The photon map as the gather reads it (nh_photon.h): the photons sorted by (grid cell key, deposit index), their
+// direction and power already decoded from PhotonData's bytes, and the uniform grid the keys come from
+struct DPhotonMap {
+    const float4 *pos;     // (x, y, z, -)
+    const float4 *dir;     // PhotonData::getDirection of the stored bytes
+    const float4 *power;   // PhotonData::getPower of the stored bytes
+    const uint64_t *keys;  // cell keys, ascending
+    int n;                 // photons stored
+    int emitted;           // m_emittedPhotons
+    float radius;          // m_photonRadius
+    float cell;            // cell side, >= radius
+    float origin[3];       // the grid's corner
+    int pad;
+};
 
 struct DScene {
     // BVH: 4 float4 per inner node, 3 float4 per primitive in leaf order
@@ -329,6 +343,9 @@ struct DScene {
     const int *shape_medium;
     int ambient_medium;
     int n_media;
+    // the photon mapper's map (nh_photon.h; read by li_photonmapper and the gather query alone): all zero until
+    // nh_photon_map_build
+    DPhotonMap pm;
 };
 
 NHD F3 ldv(const float *a, uint32_t i) { return f3(a[3 * i], a[3 * i + 1], a[3 * i + 2]); }

@@ -4,6 +4,7 @@
 // Built with -DNH_DISNEY (Makefile), like nh_disney.hip: the spot / directional branches exist only then (nh_device.h
 // kExtLights).
 #include "nh_internal.h"
+#include "nh_photon.h"
 #include "nh_shade.h"
 
 #ifndef NH_DISNEY
@@ -20,6 +21,19 @@ __global__ __launch_bounds__(64) void emitter_query_kernel(const DScene *__restr
     if (i >= q.n) return;
     const DScene &S = *Sp;
     const DEmitter e = S.emitters[q.emitter];
+    if (q.mode == NH_EMITTER_QUERY_SAMPLE_PHOTON) {  // samplePhoton, with the photon pass's `* lights.size()`
+        const float *s = q.in + 4 * (size_t)i;
+        F3 po, pd;
+        float pdf;
+        const F3 W = scl((float)S.n_emitters, emitter_sample_photon(S, e, s[0], s[1], s[2], s[3], po, pd, pdf));
+        float *o = q.out + (size_t)NH_EMITTER_QUERY_PHOTON_STRIDE * i;
+        o[0] = po.x; o[1] = po.y; o[2] = po.z;
+        o[3] = pd.x; o[4] = pd.y; o[5] = pd.z;
+        o[6] = W.x; o[7] = W.y; o[8] = W.z;
+        o[9] = pdf;
+        o[10] = o[11] = 0.f;
+        return;
+    }
     const F3 ref = f3(q.ref[3 * i], q.ref[3 * i + 1], q.ref[3 * i + 2]);
     if (q.mode == NH_EMITTER_QUERY_SAMPLE) {
         ESample es;

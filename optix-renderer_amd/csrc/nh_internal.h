@@ -310,6 +310,64 @@ void launch_medium_query(const nhd::DScene *S, const MediumQuery &q, hipStream_t
 }  // namespace nh
 }  // namespace nh_disney
 
+// ---- the photon mapper (nh_photon.hip, driven by nh_photon_api.hip) ----
+// One launch of the photon pass over paths k0 .. k0 + n_paths - 1. Count pass (offsets == null): counts[i] = deposits
+// of path k0 + i, without a cap. Write pass: deposit j of path k0 + i goes to slot base + offsets[i] + j if that is
+// below cap, and the path whose deposits reach slot cap - 1 writes *emitted = its index + 1.
+struct PhotonTrace {
+    uint64_t seed, k0;
+    int n_paths;
+    long long *counts;
+    const long long *offsets;  // exclusive prefix sums of counts
+    long long base;            // deposits of the paths before k0
+    int cap;                   // photonCount
+    float *pos;                // deposit order: 3 floats per photon
+    uint2 *bytes;              // (rgbe[0..3], theta | phi << 8)
+    uint32_t *path;
+    int *bounce;
+    int *emitted;
+};
+// the sorted map from the deposit-order arrays: keys of the deposits, then (after the sort of (key, index)) the sorted
+// records with direction and power decoded through `tab`, and the number of distinct keys
+struct PhotonFinalize {
+    int n;
+    const float *pos;
+    const uint2 *bytes;
+    const float *tab;
+    nhd::DPhotonMap pm;  // origin, cell set; pos / dir / power / keys point at the sorted arrays to fill
+    uint64_t *keys;      // unsorted keys (deposit order)
+    uint32_t *index;     // 0 .. n - 1
+    const uint32_t *sorted_index;
+    unsigned long long *cells;
+};
+// nh_photon_query's kernel: mode 0 the codec (in: 6 floats, bytes: 6, out: 6 floats), mode 1 the gather (in: 3 floats,
+// count: 1, out: 3 floats)
+struct PhotonQuery {
+    int mode, n;
+    const float *in;
+    const float *tab;
+    uint8_t *bytes;
+    int *count;
+    float *out;
+};
+namespace nh_disney {
+namespace nh {
+void launch_photon_trace(const nhd::DScene *S, const nhd::Traversal &tv, const PhotonTrace &P, int depth, hipStream_t st);
+// exclusive prefix sums (hipcub::DeviceScan), enqueued on st. tmp: photon_scan_temp_bytes(n_max) bytes, n <= n_max
+size_t photon_scan_temp_bytes(int n);
+hipError_t photon_scan(const long long *counts, long long *offsets, int n, void *tmp, size_t tmp_bytes, hipStream_t st);
+void launch_photon_keys(const PhotonFinalize &F, hipStream_t st);
+// stable radix sort of (key, index) pairs by key (hipcub::DeviceRadixSort): equal keys keep their deposit order
+hipError_t photon_sort(const uint64_t *keys_in, uint64_t *keys_out, const uint32_t *index_in, uint32_t *index_out,
+                       int n, hipStream_t st);
+void launch_photon_scatter(const PhotonFinalize &F, hipStream_t st);
+// the camera pass: one thread per (pixel, round) like launch_vol_path, PhotonMapper::Li, the same sample records
+void launch_photon_path(const nhd::DScene *S, const nhd::Traversal &tv, const PathLaunch &L, bool stats, int depth,
+                        hipStream_t st);
+void launch_photon_query(const nhd::DScene *S, const PhotonQuery &q, hipStream_t st);
+}  // namespace nh
+}  // namespace nh_disney
+
 // ---- the adaptive sampler's render loop (nh_adaptive.hip, driven by nh_adaptive_api.hip) ----
 constexpr int kAdBlock = 4;          // NORI_BLOCK_SIZE_ADAPTIVE (block.h:31)
 constexpr int kAdPaths = 16;         // paths of a pass of a full block

@@ -796,6 +796,13 @@ int nh_render(nh_ctx *c, const nh_render_req *q) {
                        "path_vol_mis integrators render it"), NH_ERR_UNSUPPORTED;
     if (c->integrator == NH_INTEGRATOR_PATH_VOL_MIS && c->n_emitters == 0)  // sampleEmitter would pick from an empty list
         return fail(c, "No Emitter in scene!"), NH_ERR_INVALID;
+    // the photon mapper's Li gathers from the map preprocess() builds (nh_photon_map_build); like the volumetric path
+    // tracers it has its own megakernel (nh_photon.hip), which also serves a wavefront request
+    const bool photon = c->integrator == NH_INTEGRATOR_PHOTONMAPPER;
+    if (photon && !c->photon.built)
+        return fail(c, "nh_render: the photon mapper needs a photon map (nh_photon_map_build)"), NH_ERR_STATE;
+    if (photon && c->sampler == NH_SAMPLER_ADAPTIVE)
+        return fail(c, "photonmapper: the adaptive sampler is not supported"), NH_ERR_UNSUPPORTED;
     // the single-bounce direct integrators always run as the megakernel: one closest hit, the light
     // sample(s) and at most one BSDF ray per path leave no bounce loop for path queues to balance. The volumetric
     // path tracers have no wavefront version yet: a wavefront request runs their megakernel (nh_volume.hip)
@@ -908,7 +915,9 @@ int nh_render(nh_ctx *c, const nh_render_req *q) {
             HIP_TRY(c, hipEventCreate(&ev.b));
             HIP_TRY(c, hipEventCreate(&ev.d));
             HIP_TRY(c, hipEventRecord(ev.a, c->stream));
-            if (volumetric)
+            if (photon)
+                nh_disney::nh::launch_photon_path(c->d_scene, c->tv, L, q->collect_stats != 0, c->depth, c->stream);
+            else if (volumetric)
                 nh_disney::nh::launch_vol_path(c->d_scene, c->tv, L, c->integrator == NH_INTEGRATOR_PATH_VOL_MIS,
                                                q->collect_stats != 0, c->depth, c->stream);
             else

@@ -14,6 +14,7 @@
 // HIP path has.
 #include "nh_dispatch.h"
 #include "nh_integrators.h"
+#include "nh_photon.h"
 #include "nh_volume.h"
 
 namespace nh_disney {
@@ -74,6 +75,7 @@ __global__ __launch_bounds__(64, 2) void path_query_kernel(const DScene *__restr
         case 6: li = li_normals<DEPTH, true, false>(S, tv, o, d, mint, maxt, sk, 64, st, queries); break;
         case 7: li = li_path_vol<DEPTH, false, false>(S, tv, rng, o, d, mint, maxt, sk, 64, st, queries); break;
         case 8: li = li_path_vol<DEPTH, false, true>(S, tv, rng, o, d, mint, maxt, sk, 64, st, queries); break;
+        case 9: li = li_photonmapper<DEPTH, false>(S, tv, rng, o, d, mint, maxt, sk, 64, st, queries); break;
         default: li = li_path_mis<DEPTH, true, false>(S, tv, rng, o, d, mint, maxt, sk, 64, st, queries); break;
     }
     if (ttest) {

@@ -34,6 +34,8 @@ int path_query_ready(nh_ctx *c, const std::string &who) {
     if (!volumetric && (c->bsdfless || c->has_media))
         return fail(c, "the scene has a participating medium or a shape without a BSDF: only the path_vol_mats and "
                        "path_vol_mis integrators render it"), NH_ERR_UNSUPPORTED;
+    if (c->integrator == NH_INTEGRATOR_PHOTONMAPPER && !c->photon.built)
+        return fail(c, who + ": the photon mapper needs a photon map (nh_photon_map_build)"), NH_ERR_STATE;
     return NH_OK;
 }
 
@@ -263,6 +265,11 @@ int nh_test_run(int device, const char *path, uint64_t seed, nh_test_result *res
             nh_bvh_get_desc(r.bvh, &bd);
             if (int rc = nh_upload_scene(r.ctx, &sd)) return ctx_fail(rc);
             if (int rc = nh_upload_bvh(r.ctx, &bd)) return ctx_fail(rc);
+            if (sd.integrator == NH_INTEGRATOR_PHOTONMAPPER) {  // Integrator::preprocess, map seed 0 as the CLI
+                nh_photon_params pp;
+                nh_scene_get_photon_params(r.scene, &pp);
+                if (int rc = nh_photon_map_build(r.ctx, &pp, 0, 0)) return ctx_fail(rc);
+            }
             double mean = 0, variance = 0;
             if (int rc = nh_ttest_scene(r.ctx, seed, 0, td.sample_count, &mean, &variance, nullptr)) return ctx_fail(rc);
             record(mean, variance, td.references[i], 0.f);

@@ -319,7 +319,7 @@ int nh_upload_scene(nh_ctx *c, const nh_scene_desc *d) {
     }
     S.n_emitters = (int)d->n_emitters;
     S.nee_finite = nh::nee_finite(d) ? 1 : 0;
-    if (d->integrator < NH_INTEGRATOR_PATH_MIS || d->integrator > NH_INTEGRATOR_PATH_VOL_MIS)
+    if (d->integrator < NH_INTEGRATOR_PATH_MIS || d->integrator > NH_INTEGRATOR_PHOTONMAPPER)
         return fail(c, "unknown integrator"), NH_ERR_INVALID;
     S.integrator = d->integrator;
     for (int i = 0; i < 3; ++i) S.ndir[i] = d->normals_direction[i];
@@ -432,6 +432,7 @@ int nh_upload_scene(nh_ctx *c, const nh_scene_desc *d) {
     c->sampler = d->sampler;
     c->adaptive_initial_uniform = std::max(1, (int)d->adaptive_initial_uniform);
     adaptive_release(c);  // block samplers of an earlier scene
+    photon_release(c);    // and its photon map
 
     // master ImageBlock
     (void)hipFree(c->fb);
@@ -534,6 +535,7 @@ int nh_upload_bvh(nh_ctx *c, const nh_bvh_desc *b) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     free_all(c->bvh_bufs);
     c->has_bvh = false;
+    photon_release(c);  // a photon map belongs to the scene and BVH it was traced in
     // the wide tree of the persistent kernels: 4-wide, or 8-wide with NH_WIDE8=1 (A/B)
     c->wide_w = std::getenv("NH_WIDE8") && std::getenv("NH_WIDE8")[0] == '1' ? 8 : 4;
     // the top of the tree the persistent kernels stage in LDS (NH_TREE_TOP: its size, 0 = none): the same bytes for

@@ -15,4 +15,7 @@ bool png_decode_rgba8(const std::string &path, std::vector<uint8_t> &out, unsign
 // malformed or unsupported files
 bool hdr_decode_rgba(const std::string &path, std::vector<float> &out, unsigned &width, unsigned &height,
                      std::string &err);
+// PhotonMapper's automatic radius (photonmapper.cpp:75-76) of a scene box: getExtents().norm() / 500.0f in fp32, the
+// squared norm grouped x*x + (y*y + z*z) as Eigen sums a Vector3f (photon_host.cpp)
+float photon_auto_radius(const float bbox_min[3], const float bbox_max[3]);
 }

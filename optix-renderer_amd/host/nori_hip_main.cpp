@@ -101,6 +101,16 @@ int main(int argc, char **argv) {
     nh_ctx *ctx = nullptr;
     if (nh_create(device, &ctx)) return die("device", "cannot create a context on the requested GPU");
     if (nh_upload_scene(ctx, &desc) || nh_upload_bvh(ctx, &bd)) return die("upload", nh_last_error(ctx));
+    if (desc.integrator == NH_INTEGRATOR_PHOTONMAPPER) {  // PhotonMapper::preprocess and its report (photonmapper.cpp:63, :152)
+        nh_photon_params pp;
+        nh_scene_get_photon_params(scene, &pp);
+        std::printf("Gathering %d photons .. ", pp.photon_count);
+        std::fflush(stdout);
+        if (nh_photon_map_build(ctx, &pp, 0, 0)) return die("photon map", nh_last_error(ctx));
+        nh_photon_stats ps;
+        nh_get_photon_stats(ctx, &ps);
+        std::printf("Emitted %d Photons.\n", ps.emitted);
+    }
     nh_render_req req;
     std::memset(&req, 0, sizeof(req));
     req.sample_begin = 0;

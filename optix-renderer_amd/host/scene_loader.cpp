@@ -220,6 +220,9 @@ struct SceneData {
     int32_t sample_count = 1;
     int32_t sampler = NH_SAMPLER_INDEPENDENT;
     int32_t adaptive_initial_uniform = 0;  // AdaptiveSampler::initialUniform after its clamp (adaptive scenes only)
+    // PhotonMapper's properties (photonmapper.cpp:39-40); photon_radius 0 = automatic (nh_scene_get_photon_params)
+    int32_t photon_count = 1000000;
+    float photon_radius = 0.f;
     std::vector<nh_shape> shapes;
     std::vector<nh_bsdf> bsdfs;
     std::vector<nh_emitter> emitters;
@@ -970,6 +973,34 @@ nh_medium make_medium(const Obj &o) {
     return m;
 }
 
+// What PhotonMapper::preprocess cannot run in the reference either, refused by name once the scene's children are read
+void check_photonmapper(const SceneData &sd) {
+    // getRandomEmitter returns nullptr and preprocess dereferences it (photonmapper.cpp:88-91)
+    if (sd.emitters.empty())
+        throw SceneError("photonmapper: a scene without an emitter is not supported (the reference dereferences "
+                         "getRandomEmitter's nullptr)");
+    // point, spot and directional lights throw in samplePhoton; the environment map's samples from a
+    // default-constructed record
+    for (const nh_emitter &e : sd.emitters)
+        if (e.type != NH_EMITTER_AREA)
+            throw SceneError("photonmapper: an emitter that is not an area light is not supported (its samplePhoton "
+                             "throws, or reads an uninitialised record)");
+    // preprocess calls bsdf->isDiffuse() unguarded and knows no medium
+    if (!sd.media.empty())
+        throw SceneError("photonmapper: a participating medium is not supported (the photon pass ignores media)");
+    for (const nh_shape &s : sd.shapes)
+        if (s.bsdf < 0) throw SceneError("photonmapper: a shape without a BSDF is not supported");
+    // the photon pass builds its BSDFQueryRecord without a uv (photonmapper.cpp:137)
+    for (const nh_bsdf &b : sd.bsdfs)
+        if ((b.type == NH_BSDF_DIFFUSE || b.type == NH_BSDF_DISNEY) && b.albedo_texture)
+            throw SceneError("photonmapper: a textured diffuse or Disney albedo is not supported (the photon pass "
+                             "samples the BSDF without a uv)");
+    if (sd.sampler == NH_SAMPLER_ADAPTIVE) throw SceneError("photonmapper: the adaptive sampler is not supported");
+    if (sd.photon_count < 1) throw SceneError("photonmapper: photonCount below 1 is not supported");
+    if (!(sd.photon_radius >= 0.f) || !std::isfinite(sd.photon_radius))
+        throw SceneError("photonmapper: a negative or non-finite photonRadius is not supported");
+}
+
 void build_scene(const Obj &scene, const std::string &base_dir, SceneData &sd) {
     bool have_camera = false, have_integrator = false, have_sampler = false, have_ambient = false;
     set_filter(sd.filter, 0, 2.0f, 0.5f, 1.0f / 3.0f, 1.0f / 3.0f);
@@ -990,6 +1021,11 @@ void build_scene(const Obj &scene, const std::string &base_dir, SceneData &sd) {
                 sd.integrator = NH_INTEGRATOR_NORMALS;
                 const V3 dir = ch.props.get_point("direction", v3(0, 0, 1));
                 sd.normals_dir[0] = dir.x; sd.normals_dir[1] = dir.y; sd.normals_dir[2] = dir.z;
+            }
+            else if (ch.type == "photonmapper") {  // PhotonMapper (photonmapper.cpp:36-41)
+                sd.integrator = NH_INTEGRATOR_PHOTONMAPPER;
+                sd.photon_count = ch.props.get_int("photonCount", 1000000);
+                sd.photon_radius = ch.props.get_float("photonRadius", 0.0f);
             }
             else throw SceneError("integrator \"" + ch.type + "\" is not supported by the HIP path");
         } else if (ch.tag == "camera") {
@@ -1170,6 +1206,7 @@ void build_scene(const Obj &scene, const std::string &base_dir, SceneData &sd) {
             throw SceneError("Scene::addChild(<" + ch.tag + ">) is not supported");
         }
     }
+    if (have_integrator && sd.integrator == NH_INTEGRATOR_PHOTONMAPPER) check_photonmapper(sd);
     if (!have_integrator) throw SceneError("No integrator was specified!");
     if (!have_camera) throw SceneError("No camera was specified!");
     if (!sd.emitter_ext.empty()) sd.emitter_ext.resize(sd.emitters.size());  // one entry per emitter
@@ -1508,6 +1545,35 @@ int nh_scene_set_integrator(nh_scene *scene, int32_t integrator) {
         return NH_ERR_INVALID;
     }
     scene->data->integrator = integrator;
+    return NH_OK;
+}
+
+int nh_scene_get_photon_params(const nh_scene *scene, nh_photon_params *out) {
+    if (!scene || !out) { nh::set_host_error("null argument"); return NH_ERR_INVALID; }
+    const nh::SceneData &sd = *scene->data;
+    out->photon_count = sd.photon_count;
+    out->photon_radius = sd.photon_radius;
+    if (sd.photon_radius == 0.f) {
+        // scene->getBoundingBox(): the BVH's box, the union of the shapes' boxes (bvh.cpp addShape)
+        float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (const nh_shape &s : sd.shapes)
+            for (int k = 0; k < 3; ++k) {
+                mn[k] = std::min(mn[k], s.bbox_min[k]);
+                mx[k] = std::max(mx[k], s.bbox_max[k]);
+            }
+        out->photon_radius = sd.shapes.empty() ? 0.f : nh::photon_auto_radius(mn, mx);
+    }
+    return NH_OK;
+}
+
+int nh_scene_set_photon_params(nh_scene *scene, const nh_photon_params *params) {
+    if (!scene || !params || params->photon_count < 1 || !(params->photon_radius >= 0.f) ||
+        !std::isfinite(params->photon_radius)) {
+        nh::set_host_error("invalid photon parameters");
+        return NH_ERR_INVALID;
+    }
+    scene->data->photon_count = params->photon_count;
+    scene->data->photon_radius = params->photon_radius;
     return NH_OK;
 }
 

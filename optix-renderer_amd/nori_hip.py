@@ -286,6 +286,42 @@ _sig("nh_ttest_scene", _i32, _vp, C.c_uint64, C.c_int64, _i32, _dp, _dp, _fp)
 _sig("nh_ttest_bsdf", _i32, _vp, C.POINTER(nh_bsdf), _fp, _f, C.c_uint64, _i32, _dp, _dp, _fp)
 _sig("nh_test_run", _i32, C.c_int, C.c_char_p, C.c_uint64, C.POINTER(nh_test_result), _i32, _i32p)
 
+
+# ---- the photon mapper (photonmapper.cpp) ----
+INTEGRATOR_PHOTONMAPPER = 9
+EMITTER_QUERY_SAMPLE_PHOTON, EMITTER_QUERY_PHOTON_STRIDE = 3, 12
+PHOTON_QUERY_CODEC, PHOTON_QUERY_GATHER = 0, 1
+PHOTON_STREAM = 1 << 32          # NH_PHOTON_STREAM: photon path k draws from path_rng(seed, PHOTON_STREAM, k)
+PHOTON_DEFAULT_BATCH = 1 << 18   # NH_PHOTON_DEFAULT_BATCH
+
+
+class nh_photon_params(C.Structure):
+    _fields_ = [("photon_count", _i32), ("photon_radius", _f)]
+
+
+class nh_photon_stats(C.Structure):
+    _fields_ = [("stored", _i32), ("emitted", _i32), ("radius", _f), ("cell_size", _f),
+                ("occupied_cells", C.c_uint64)]
+
+
+_u8p = C.POINTER(C.c_uint8)
+_sig("nh_scene_get_photon_params", _i32, _vp, C.POINTER(nh_photon_params))
+_sig("nh_scene_set_photon_params", _i32, _vp, C.POINTER(nh_photon_params))
+_sig("nh_photon_tables", _i32, _fp, _fp, _fp, _fp, _fp)
+_sig("nh_photon_map_build", _i32, _vp, C.POINTER(nh_photon_params), C.c_uint64, _i32)
+_sig("nh_get_photon_stats", _i32, _vp, C.POINTER(nh_photon_stats))
+_sig("nh_get_photons", _i32, _vp, _i32, _i32, _fp, _fp, _fp, _u8p, _i32p, _i32p)
+_sig("nh_photon_query", _i32, _vp, _i32, _i32, _fp, _u8p, _i32p, _fp)
+
+
+def photon_tables() -> dict:
+    """nh_photon_tables: PhotonData's five 256-entry decode tables (photon.cpp:30-41), float32."""
+    t = {k: np.zeros(256, np.float32) for k in ("cos_theta", "sin_theta", "cos_phi", "sin_phi", "exp")}
+    _host_check(_lib.nh_photon_tables(*[_fptr(t[k]) for k in ("cos_theta", "sin_theta", "cos_phi", "sin_phi", "exp")]),
+                "photon_tables")
+    return t
+
+
 lib = _lib
 _hip_used = False  # set by the first call that initialises the HIP runtime (device_count, Context)
 
@@ -346,6 +382,18 @@ class Scene:
 
     def set_integrator(self, integ: int):
         _host_check(_lib.nh_scene_set_integrator(self._h, integ), "set_integrator")
+
+    def photon_params(self) -> tuple:
+        """nh_scene_get_photon_params: (photonCount, photonRadius) of the scene's photon mapper, the radius resolved
+        (0 = automatic becomes the scene box's diagonal / 500, photonmapper.cpp:75-76)."""
+        p = nh_photon_params()
+        _host_check(_lib.nh_scene_get_photon_params(self._h, C.byref(p)), "get_photon_params")
+        return int(p.photon_count), float(np.float32(p.photon_radius))
+
+    def set_photon_params(self, photon_count: int, photon_radius: float = 0.0):
+        """nh_scene_set_photon_params: override photonCount and photonRadius (0 = automatic)."""
+        p = nh_photon_params(photon_count, photon_radius)
+        _host_check(_lib.nh_scene_set_photon_params(self._h, C.byref(p)), "set_photon_params")
 
     def set_bsdf(self, shape: int, **kw):
         b = nh_bsdf()
@@ -576,12 +624,78 @@ class Context:
         if rc != NH_OK:
             raise NoriError(f"{what}: {_lib.nh_last_error(self._h).decode()} (rc={rc})")
 
-    def upload(self, scene: Scene, bvh: Bvh):
+    def upload(self, scene: Scene, bvh: Bvh, photon_map: bool = True):
+        """Uploads the scene and its BVH; a photon-mapper scene also builds its photon map with seed 0 (photon_map=False
+        leaves that to build_photon_map)."""
         self.scene = scene
         d = scene.desc
         self._check(_lib.nh_upload_scene(self._h, C.byref(d)), "upload_scene")
         b = bvh.desc
         self._check(_lib.nh_upload_bvh(self._h, C.byref(b)), "upload_bvh")
+        if photon_map and d.integrator == INTEGRATOR_PHOTONMAPPER:  # Integrator::preprocess, map seed 0
+            self.build_photon_map(seed=0)
+
+    def build_photon_map(self, seed: int = 0, batch_paths: int = 0, photon_count: int = None,
+                         photon_radius: float = None) -> dict:
+        """nh_photon_map_build on the uploaded scene: PhotonMapper::preprocess with photon path k on the stream
+        (seed, PHOTON_STREAM, k). photon_count / photon_radius default to the scene's; batch_paths (paths per launch,
+        0 = PHOTON_DEFAULT_BATCH) changes nothing in the result. Returns photon_stats()."""
+        n, r = self.scene.photon_params()
+        p = nh_photon_params(n if photon_count is None else photon_count, r if photon_radius is None else photon_radius)
+        self._check(_lib.nh_photon_map_build(self._h, C.byref(p), seed, batch_paths), "photon_map_build")
+        return self.photon_stats()
+
+    def photon_stats(self) -> dict:
+        """nh_get_photon_stats: stored, emitted (E), radius, cell_size, occupied_cells of the context's map."""
+        s = nh_photon_stats()
+        self._check(_lib.nh_get_photon_stats(self._h, C.byref(s)), "get_photon_stats")
+        return {"stored": int(s.stored), "emitted": int(s.emitted), "radius": np.float32(s.radius),
+                "cell_size": np.float32(s.cell_size), "occupied_cells": int(s.occupied_cells)}
+
+    def photons(self, first: int = 0, n: int = None) -> dict:
+        """nh_get_photons: photons first .. first + n - 1 in deposit order. {"position", "direction", "power": (n, 3)
+        float32 (direction and power decoded from the stored bytes), "bytes": (n, 6) uint8 (theta, phi, rgbe),
+        "path", "bounce": (n,) int32}."""
+        if n is None:
+            n = self.photon_stats()["stored"] - first
+        out = {"position": np.zeros((n, 3), np.float32), "direction": np.zeros((n, 3), np.float32),
+               "power": np.zeros((n, 3), np.float32), "bytes": np.zeros((n, 6), np.uint8),
+               "path": np.zeros(n, np.int32), "bounce": np.zeros(n, np.int32)}
+        self._check(_lib.nh_get_photons(self._h, first, n, _fptr(out["position"]), _fptr(out["direction"]),
+                                        _fptr(out["power"]), out["bytes"].ctypes.data_as(_u8p),
+                                        out["path"].ctypes.data_as(_i32p), out["bounce"].ctypes.data_as(_i32p)),
+                    "get_photons")
+        return out
+
+    def photon_codec(self, direction: np.ndarray, power: np.ndarray) -> dict:
+        """nh_photon_query, PHOTON_QUERY_CODEC: PhotonData's constructor and getters on the device. {"bytes": (n, 6)
+        uint8 (theta, phi, rgbe), "direction", "power": (n, 3) float32 decoded from them}. Needs no scene."""
+        inp = np.ascontiguousarray(np.concatenate([np.asarray(direction, np.float32).reshape(-1, 3),
+                                                   np.asarray(power, np.float32).reshape(-1, 3)], axis=1))
+        n = len(inp)
+        b, o = np.zeros((n, 6), np.uint8), np.zeros((n, 6), np.float32)
+        self._check(_lib.nh_photon_query(self._h, PHOTON_QUERY_CODEC, n, _fptr(inp), b.ctypes.data_as(_u8p), None,
+                                         _fptr(o)), "photon_query")
+        return {"bytes": b, "direction": o[:, 0:3].copy(), "power": o[:, 3:6].copy()}
+
+    def photon_gather(self, points: np.ndarray) -> dict:
+        """nh_photon_query, PHOTON_QUERY_GATHER: per point the number of photons within the map's radius (strict,
+        fp32) and the fp32 sum of their decoded powers in the gather's order. {"count": (n,) int32, "power": (n, 3)}."""
+        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        n = len(pts)
+        cnt, o = np.zeros(n, np.int32), np.zeros((n, 3), np.float32)
+        self._check(_lib.nh_photon_query(self._h, PHOTON_QUERY_GATHER, n, _fptr(pts), None,
+                                         cnt.ctypes.data_as(_i32p), _fptr(o)), "photon_query")
+        return {"count": cnt, "power": o}
+
+    def sample_photon(self, emitter: int, sample: np.ndarray) -> dict:
+        """nh_emitter_query, EMITTER_QUERY_SAMPLE_PHOTON: samplePhoton of area light `emitter` for sample (n, 4) =
+        (sample1, sample2). {"o", "d", "W": (n, 3), "pdf": (n,)}; W includes the photon pass's `* lights.size()`."""
+        s = np.ascontiguousarray(sample, dtype=np.float32).reshape(-1, 4)
+        o = np.zeros((len(s), EMITTER_QUERY_PHOTON_STRIDE), np.float32)
+        self._check(_lib.nh_emitter_query(self._h, emitter, EMITTER_QUERY_SAMPLE_PHOTON, len(s), None, _fptr(s),
+                                          _fptr(o)), "emitter_query")
+        return {"o": o[:, 0:3].copy(), "d": o[:, 3:6].copy(), "W": o[:, 6:9].copy(), "pdf": o[:, 9].copy()}
 
     def render(self, s0: int, s1: int, seed: int = 0, blocks=None, traversal: int = TRAVERSAL_REFERENCE,
                clear: bool = False, stats: bool = False, mode: int = MODE_MEGAKERNEL):
