@@ -419,6 +419,12 @@ typedef struct nh_render_stats {
        1 the general kernels, 2 the diffuse area-light ones (path_mis, every BSDF diffuse with a constant albedo, every
        light an area light on a mesh, no envmap, normal map or thin lens; NH_BOUNCE_TRAITS=0 forces 1) */
     uint64_t bounce_traits;
+    /* 1 when bounce 0 of the last render took its camera rays' first closest hit with the per-block candidate masks
+       (nh_primary_masks): a wavefront render on the RR-ahead bounce kernels, at most 64 primitive records staged in
+       LDS, a pinhole camera, no collect_stats; NH_PRIMARY_MASKS=0 forces 0. Every nh_render clears it (so it reads 0
+       after a megakernel render) and a wavefront chunk sets it when it starts on a path pool, which for an
+       asynchronous call can be after nh_render returns: read it after nh_synchronize. */
+    uint64_t primary_masks;
 } nh_render_stats;
 
 typedef struct nh_scene nh_scene;
@@ -478,6 +484,16 @@ int nh_debug_transform(const char *request, float *out, int32_t cap);
 int nh_bvh_build(const nh_scene_desc *scene, int32_t n_threads, nh_bvh **out);
 int nh_bvh_get_desc(const nh_bvh *bvh, nh_bvh_desc *out);
 void nh_bvh_free(nh_bvh *bvh);
+
+/* Per-block candidate masks of the camera rays' first closest hit (host/primary_masks.cpp; host only). records:
+ * n_records primitive records of 12 floats, as the device reads them -- a triangle (p0, .) (p1, .) (p2, bits), a sphere
+ * (centre, radius) (., ., ., .) (., ., ., bits) with bit 0 of the last word's integer pattern set. blocks: n_blocks ids
+ * (by * nbx + bx) of 32x32 image blocks. *built = 1 and masks[i] bit k set when a camera ray through block blocks[i],
+ * grown by nh_primary_mask_pad pixels, can hit record k; *built = 0 (masks untouched) when the scene has more than 64
+ * records or the camera a lens: nh_render then tests every record, as it does with NH_PRIMARY_MASKS=0. */
+int nh_primary_masks(const nh_camera *camera, const float *records, int32_t n_records, const int32_t *blocks,
+                     int32_t n_blocks, uint64_t *masks, int32_t *built);
+int32_t nh_primary_mask_pad(int32_t width, int32_t height);
 
 /* ImageBlock::toBitmap (src/utils/block.cpp:76-82): rgbw with border -> W*H*3 rgb */
 int nh_framebuffer_to_rgb(const float *rgbw, int32_t width, int32_t height, int32_t border, float *rgb);

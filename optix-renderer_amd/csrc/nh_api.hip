@@ -81,6 +81,7 @@ void nh_destroy(nh_ctx *c) {
     (void)hipFree(c->fb);
     (void)hipFree(c->rec);
     c->px.release();
+    (void)hipFree(c->pmask);
     (void)hipFree(c->block_rank);
     (void)hipFree(c->staging);
     (void)hipFree(c->counters);

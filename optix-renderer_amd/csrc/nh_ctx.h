@@ -197,6 +197,14 @@ struct nh_ctx {
     // (all 0: tables not staged)
     float4 *small_image = nullptr;
     int small_tab[5] = {0, 0, 0, 0, 0};
+    // Candidate masks of the camera rays' first closest hit (WfLaunch::pmask, host/primary_masks.cpp): built by
+    // nh_render (ensure_primary_masks) from the uploaded camera, the primitive records (kept here when there are at
+    // most 64) and the pixel list's blocks; every upload and every new pixel list frees them (drop_primary_masks), so
+    // pmask is null or the table of the current scene and list. It stays null when the feature is absent.
+    nh_camera camera{};
+    std::vector<float> h_prims;  // 12 floats per record, as uploaded; empty: more than 64 records
+    unsigned long long *pmask = nullptr;
+    bool pmask_known = false;
     float *fb = nullptr;
     size_t fb_floats = 0;
     float *rec = nullptr;  // (r, g, b) per sample
@@ -217,6 +225,13 @@ struct nh_ctx {
     bool fb_ev_set = false;
     uint64_t stats_comm_inits = 0;  // communicator cliques this context created as reduce root
 };
+
+// Frees the context's candidate-mask table. The caller has drained the pipeline (no chunk in flight reads it).
+inline void drop_primary_masks(nh_ctx *c) {
+    (void)hipFree(c->pmask);
+    c->pmask = nullptr;
+    c->pmask_known = false;
+}
 
 // A launcher of a kernel that shades, from the set nh_upload_scene chose for the context's scene (nh_internal.h)
 #define NH_LAUNCH(c, fn) ((c)->disney ? nh_disney::nh::fn : nh::fn)

@@ -202,6 +202,11 @@ struct WfLaunch {
     uint32_t *trav_spill;
     int spill_depth;
     unsigned long long *counters;
+    // Candidate masks of the camera rays' first closest hit (host/primary_masks.cpp), one per 32x32 block of the image's
+    // block grid (by * nbx + bx; nbx = pmask_nbx), bit k = primitive record k; null: every record is tested. Read by
+    // first_vertex of the non-STATS fused bounce kernels only.
+    const unsigned long long *pmask;
+    int pmask_nbx;
 };
 // persistent traversal grid: 16 workgroups of 128 lanes per CU (the 8 waves/SIMD its registers allow)
 constexpr int kPersistentBlocks = 256 * 16;

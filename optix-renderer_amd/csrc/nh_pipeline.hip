@@ -6,6 +6,7 @@
 #include <thread>
 #include <type_traits>
 
+#include "../host/gpu_layout.h"
 #include "nh_ctx.h"
 
 // ============================================================================================
@@ -270,6 +271,12 @@ static int pool_start(nh_ctx *c, WfPool &p, const WfJob &job) {
     p.trait = p.rr && c->diffuse_area && c->small_tab[0] > 0 && j.ordered && !p.sorted;
     if (const char *e = std::getenv("NH_BOUNCE_TRAITS")) p.trait = p.trait && e[0] != '0';
     c->stats.bounce_traits = p.rr ? (p.trait ? 2 : 1) : 0;
+    // bounce 0's candidate masks (first_vertex of the RR-ahead kernels; the counting kernels test every record)
+    const char *pm = std::getenv("NH_PRIMARY_MASKS");
+    const bool masks = p.rr && c->pmask && !j.stats && !(pm && pm[0] == '0');
+    L.pmask = masks ? c->pmask : nullptr;
+    L.pmask_nbx = c->nbx;
+    c->stats.primary_masks = masks ? 1 : 0;
     c->stats.fused_bounce = p.fused ? 1 : 0;
     c->stats.node_bytes = p.wide ? 16 * nhd::kWideF4 * (c->wide_w / 4) : 64;
     c->stats.lds_scene = small && !p.persistent && c->depth <= 16 ? 1 : 0;  // the SMALL instantiations (DEPTH 16)
@@ -773,6 +780,37 @@ static int ensure_pixel_list(nh_ctx *c, const nh_render_req *q) {
         return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     std::swap(c->px, n);
+    drop_primary_masks(c);  // the masks follow the list's blocks (the pipeline was drained above)
+    return NH_OK;
+}
+
+// The camera rays' candidate masks (WfLaunch::pmask) for the uploaded scene and the current pixel list: one entry per
+// block of the image's block grid, those of the rendered blocks filled in. Absent (null) unless the scene is small
+// enough for the LDS-staged kernels and nh::primary_masks accepts it (at most 64 records, a pinhole camera).
+static int ensure_primary_masks(nh_ctx *c) {
+    if (c->pmask_known) return NH_OK;
+    if (int rc = pipeline_drain(c)) return rc;  // chunks in flight read the current table
+    drop_primary_masks(c);
+    c->pmask_known = true;
+    const size_t scene_bytes = 16 * (size_t)(c->n_node_f4 + c->n_prim_f4) + 8 * (size_t)c->n_leaves;
+    if (c->h_prims.empty() || scene_bytes > kSmallSceneBytes) return NH_OK;
+    std::vector<int32_t> blocks = c->px.list_key;
+    if (blocks.empty())
+        for (int i = 0; i < c->nbx * c->nby; ++i) blocks.push_back(i);
+    std::vector<uint64_t> m;
+    if (!nh::primary_masks(c->camera, reinterpret_cast<const nh::f4 *>(c->h_prims.data()), (int)(c->h_prims.size() / 12),
+                           blocks.data(), (int)blocks.size(), m))
+        return NH_OK;
+    std::vector<unsigned long long> grid((size_t)c->nbx * c->nby, 0ull);
+    for (size_t i = 0; i < blocks.size(); ++i) grid[(size_t)blocks[i]] = m[i];
+    unsigned long long *d = nullptr;
+    HIP_TRY(c, hipMalloc(&d, std::max<size_t>(grid.size(), 1) * sizeof(unsigned long long)));
+    const hipError_t e = hipMemcpy(d, grid.data(), grid.size() * sizeof(unsigned long long), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        HIP_TRY(c, e);
+    }
+    c->pmask = d;
     return NH_OK;
 }
 
@@ -820,7 +858,9 @@ int nh_render(nh_ctx *c, const nh_render_req *q) {
     if (c->sampler == NH_SAMPLER_ADAPTIVE) return render_adaptive(c, q);
     rc = ensure_pixel_list(c, q);
     if (rc) return rc;
+    if (wavefront && (rc = ensure_primary_masks(c))) return rc;
     c->stats.node_bytes = 64;  // binary tree unless a wavefront pool picks the 4-wide one
+    c->stats.primary_masks = 0;
     c->stats.trace_fused = 0;
     c->stats.lds_scene = 0;
     c->stats.fused_bounce = 0;

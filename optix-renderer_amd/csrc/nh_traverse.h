@@ -249,12 +249,18 @@ NHD bool prim_is_tri(float4 c) { return (__float_as_int(c.w) & kPrimSphere) == 0
 NHD int prim_material(float4 c) { return (__float_as_int(c.w) >> kPrimMatShift) & 3; }
 
 // Test the primitives of one leaf. Returns true when an any-hit query is answered.
-template <bool ANY, bool STATS, bool PAIRS = false>
+// MASKED (pair records, camera rays at bounce 0): cand bit k says record k can accept this ray at all (the host's
+// per-block candidate masks, host/primary_masks.cpp; all ones: no table). A pair record neither of whose bits is set
+// is skipped -- by the whole wave when no lane needs it. Exact: a record whose test could not have accepted the ray
+// changes neither the answer nor the maxt the other tests see. (k & 63: real masks exist for at most 64 records.)
+template <bool ANY, bool STATS, bool PAIRS = false, bool MASKED = false>
 NHD bool leaf_test(const Traversal &tv, int leaf, F3 o, F3 d, float mint, float &maxt, Hit &best, bool &found,
-                   TravStats &st) {
+                   TravStats &st, unsigned long long cand = ~0ull) {
     const int2 lf = tv.leaves[leaf];
     if constexpr (PAIRS) {  // interleaved pair records: no AoS -> pair shuffles
         for (int k = lf.x, e = lf.x + lf.y; k < e; k += 2) {
+            if constexpr (MASKED && !STATS)
+                if (!((cand >> (k & 63)) & 3ull)) continue;
             const float4 *pp = tv.ppairs + (size_t)kPairF4 * k;
             const float4 q0 = pp[0], q1 = pp[1], q2 = pp[2], q3 = pp[3], q4 = pp[4], q5 = pp[5];
             const P3 p0{f2{q0.x, q0.y}, f2{q0.z, q0.w}, f2{q1.x, q1.y}};
@@ -410,11 +416,11 @@ NHD bool leaf_test_coop(const Traversal &tv, int leaf, F3 o, F3 d, float mint, f
     return false;
 }
 
-template <bool ANY, bool STATS, bool PAIRS, int G>
+template <bool ANY, bool STATS, bool PAIRS, int G, bool MASKED = false>
 NHD bool leaf_any(const Traversal &tv, int leaf, F3 o, F3 d, float mint, float &maxt, Hit &best, bool &found,
-                  TravStats &st) {
+                  TravStats &st, unsigned long long cand = ~0ull) {
     if constexpr (G > 1) return leaf_test_coop<ANY, STATS, G>(tv, leaf, o, d, mint, maxt, best, found, st);
-    else return leaf_test<ANY, STATS, PAIRS>(tv, leaf, o, d, mint, maxt, best, found, st);
+    else return leaf_test<ANY, STATS, PAIRS, MASKED>(tv, leaf, o, d, mint, maxt, best, found, st, cand);
 }
 
 // Inner-node fields read as scalars straight from the node record (float i of node n: nf[i], nf = the node's first
@@ -454,9 +460,11 @@ NHD void node_box_tests(const float *nf, F3 o, F3 d, F3 r, float mint, float max
 // popped, with the maxt of that moment -- the reference's visit-time test verbatim.
 // G > 1: the ray is carried by a G-lane group (leaf primitives tested cooperatively, leaf_test_coop).
 // RCP: the direction's reciprocals by dir_rcp (the same values as the divisions) instead of three IEEE divisions.
-template <int DEPTH, bool ORDERED, bool ANY, bool STATS, bool PAIRS = false, int G = 1, bool RCP = false>
+// MASKED: cand holds the ray's candidate records (leaf_test); the root, node and box tests and the visit order are the same.
+template <int DEPTH, bool ORDERED, bool ANY, bool STATS, bool PAIRS = false, int G = 1, bool RCP = false,
+          bool MASKED = false>
 NHD bool trace(const Traversal &tv, const DScene &S, F3 o, F3 d, float mint, float maxt, Hit &best, uint32_t *stk,
-               int stride, TravStats &st) {
+               int stride, TravStats &st, unsigned long long cand = ~0ull) {
     // adaptive ray epsilon (bvh.cpp:407-410)
     if (mint == kEps) mint = e_max(mint, mint * e_max(fabsf(o.x), e_max(fabsf(o.y), fabsf(o.z))));
     // counters: one lane of a group carrying the ray counts for it
@@ -475,7 +483,7 @@ NHD bool trace(const Traversal &tv, const DScene &S, F3 o, F3 d, float mint, flo
                         d, r, mint, maxt, near_t))
         return false;
     if (S.root_kind == 2) {
-        bool any = leaf_any<ANY, STATS, PAIRS, G>(tv, 0, o, d, mint, maxt, best, found, st);
+        bool any = leaf_any<ANY, STATS, PAIRS, G, MASKED>(tv, 0, o, d, mint, maxt, best, found, st, cand);
         return ANY ? any : found;
     }
     int sp = 0;
@@ -505,7 +513,7 @@ NHD bool trace(const Traversal &tv, const DScene &S, F3 o, F3 d, float mint, flo
                 cur = next;
                 continue;
             }
-            if (leaf_any<ANY, STATS, PAIRS, G>(tv, ~next, o, d, mint, maxt, best, found, st)) return true;
+            if (leaf_any<ANY, STATS, PAIRS, G, MASKED>(tv, ~next, o, d, mint, maxt, best, found, st, cand)) return true;
             break;
         }
         // pop: re-test the deferred child against the current maxt
@@ -522,7 +530,7 @@ NHD bool trace(const Traversal &tv, const DScene &S, F3 o, F3 d, float mint, flo
                 cur = ref;
                 break;
             }
-            if (leaf_any<ANY, STATS, PAIRS, G>(tv, ~ref, o, d, mint, maxt, best, found, st)) return true;
+            if (leaf_any<ANY, STATS, PAIRS, G, MASKED>(tv, ~ref, o, d, mint, maxt, best, found, st, cand)) return true;
         }
         if (cur < 0) break;
     }

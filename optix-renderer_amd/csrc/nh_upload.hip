@@ -86,6 +86,8 @@ int nh_upload_scene(nh_ctx *c, const nh_scene_desc *d) {
     free_all(c->bvh_bufs);
     c->has_scene = c->has_bvh = false;
     c->px.have_list = false;
+    drop_primary_masks(c);
+    c->camera = d->camera;
 
     std::vector<DShape> ds(d->n_shapes);
     for (uint32_t i = 0; i < d->n_shapes; ++i) {
@@ -555,6 +557,11 @@ int nh_upload_bvh(nh_ctx *c, const nh_bvh_desc *b) {
     c->n_node_f4 = (int)g.nodes.size();
     c->n_leaves = (int)g.leaves.size();
     c->n_prim_f4 = (int)g.prims.size() - 3;  // (without the zero record past the end)
+    // the records the camera rays' candidate masks are built from (nh_pipeline.hip ensure_primary_masks)
+    drop_primary_masks(c);
+    c->h_prims.clear();
+    if (c->n_prim_f4 > 0 && c->n_prim_f4 / 3 <= 64)
+        c->h_prims.assign(&g.prims[0].x, &g.prims[0].x + 4 * (size_t)c->n_prim_f4);
     const nh::f4 *nodes = nullptr, *prims = nullptr, *wide = nullptr;
     const nh::i2 *leaves = nullptr;
     if ((rc = upload(c, c->bvh_bufs, g.nodes.data(), g.nodes.size(), &nodes))) return rc;

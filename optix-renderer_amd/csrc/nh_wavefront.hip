@@ -133,12 +133,14 @@ __device__ __forceinline__ void unpack_ray(float4 &ro, float4 &rd) {
 // pixel jitter, the unused aperture sample, PerspectiveCamera::sampleRay (perspective.cpp:97-141).
 // Bounce 0 evaluates it in place -- in the extend kernel for the ray, again in the shade kernel
 // for its state -- instead of a generate kernel writing ~100 B per path that both read back.
+// blk: where given, the pixel's 32x32 block in the image's block grid (the index of its candidate mask, L.pmask).
 template <bool DOF = true>
 __device__ __forceinline__ void camera_sample(const DScene &S, const WfLaunch &L, int p, Rng &rng, float4 &ro,
-                                              float4 &rd, float &jx, float &jy) {
+                                              float4 &rd, float &jx, float &jy, int *blk = nullptr) {
     const int k = p / L.n_list, i = p - k * L.n_list;
     const int pix = L.pixel_list[i];
     const int py = pix / S.width, px = pix - py * S.width;
+    if (blk) *blk = (py >> 5) * L.pmask_nbx + (px >> 5);
     rng = path_rng(L.seed, (uint64_t)pix, (uint64_t)(L.s0 + k));
     jx = rng.next1d();
     jy = rng.next1d();
@@ -1222,7 +1224,21 @@ __device__ __forceinline__ bool first_vertex(const DScene &S, const ST &T, const
                                              unsigned long long &q_e) {
     float4 ro, rd;
     float jx, jy;
-    camera_sample<!TRAIT>(S, L, s, v.rng, ro, rd, jx, jy);
+    // the ray's candidate records (leaf_test<.., MASKED>): its block's mask, or every record without a table. The
+    // counting kernels test every record: their counts are the reference traversal's.
+#ifndef NH_AB_NO_PMASK  // cost attribution builds only: the masks compiled out
+    constexpr bool MASKED = !STATS;
+#else
+    constexpr bool MASKED = false;
+#endif
+    unsigned long long cand = ~0ull;
+    if constexpr (MASKED) {
+        int blk;
+        camera_sample<!TRAIT>(S, L, s, v.rng, ro, rd, jx, jy, &blk);
+        if (L.pmask) cand = L.pmask[blk];
+    } else {
+        camera_sample<!TRAIT>(S, L, s, v.rng, ro, rd, jx, jy);
+    }
     if (L.jit) L.jit[s] = make_float2(jx, jy);
     v.org = xyz(ro);
     v.d = xyz(rd);
@@ -1235,7 +1251,8 @@ __device__ __forceinline__ bool first_vertex(const DScene &S, const ST &T, const
     const bool live = rd.w >= ro.w;
     q_e += live ? 1 : 0;
     const bool found =
-        live && trace<16, ORDERED, false, STATS, true, 1, TRAIT>(tv, S, v.org, v.d, ro.w, rd.w, h, stk, stride, st_e);
+        live && trace<16, ORDERED, false, STATS, true, 1, TRAIT, MASKED>(tv, S, v.org, v.d, ro.w, rd.w, h, stk, stride,
+                                                                        st_e, cand);
     if (!shade_head<NMAP, TRAIT>(S, T, tv, v, h, found, 0.f, its)) {
         write_radiance(L, v);
         return false;

@@ -59,4 +59,13 @@ LensTables lens_tables(int w, int h);
 
 bool nee_finite(const nh_scene_desc *d);
 
+// Per-block candidate masks of the camera rays' first closest hit (primary_masks.cpp). prims: the n_records primitive
+// records as the device reads them (3 f4 each, record index k); blocks: ids (by * nbx + bx) of the rendered 32x32
+// blocks. masks[i] bit k: record k can be hit by a camera ray of block blocks[i]. False, and no table, when the scene
+// has more than 64 records or the camera a lens (or its transform cannot be inverted).
+bool primary_masks(const nh_camera &cam, const f4 *prims, int n_records, const int32_t *blocks, int n_blocks,
+                   std::vector<uint64_t> &masks);
+// the pad in pixels a block's rectangle is grown by: at least 2, a 256th of the larger image side
+int primary_mask_pad(int width, int height);
+
 }  // namespace nh

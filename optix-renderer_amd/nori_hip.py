@@ -204,7 +204,7 @@ class nh_render_stats(C.Structure):
                                   "tail_coop_cycles_shadow", "tail_coop_cycles_closest", "tail_coop_cycles_head",
                                   "tail_coop_bounces", "bounce_cycles_load", "bounce_cycles_body",
                                   "bounce_cycles_shadow", "bounce_cycles_closest", "bounce_cycles_head",
-                                  "bounce_cycles_store", "bounce_bounces", "bounce_traits")]
+                                  "bounce_cycles_store", "bounce_bounces", "bounce_traits", "primary_masks")]
 
 
 def _sig(name, res, *args):
@@ -233,6 +233,9 @@ _sig("nh_debug_transform", _i32, C.c_char_p, _fp, _i32)
 _sig("nh_bvh_build", _i32, C.POINTER(nh_scene_desc), _i32, C.POINTER(_vp))
 _sig("nh_bvh_get_desc", _i32, _vp, C.POINTER(nh_bvh_desc))
 _sig("nh_bvh_free", None, _vp)
+_sig("nh_primary_masks", _i32, C.POINTER(nh_camera), _fp, _i32, C.POINTER(_i32), _i32, C.POINTER(C.c_uint64),
+     C.POINTER(_i32))
+_sig("nh_primary_mask_pad", _i32, _i32, _i32)
 _sig("nh_framebuffer_to_rgb", _i32, _fp, _i32, _i32, _i32, _fp)
 _sig("nh_write_pfm", _i32, C.c_char_p, _fp, _i32, _i32)
 _sig("nh_image_load_png", _i32, C.c_char_p, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(_i32), C.POINTER(_i32))
@@ -884,6 +887,25 @@ def tile_shard(width: int, height: int, world: int, rank: int) -> list:
     round-robin to ranks: the multi-GPU partition of the image."""
     nbx, nby = (width + 31) // 32, (height + 31) // 32
     return [b for b in range(nbx * nby) if b % world == rank]
+
+
+def primary_mask_pad(width: int, height: int) -> int:
+    """nh_primary_mask_pad: the pixels a block's rectangle is grown by on every side."""
+    return int(_lib.nh_primary_mask_pad(width, height))
+
+
+def primary_masks(camera: nh_camera, records: np.ndarray, blocks):
+    """nh_primary_masks: per block of `blocks` (ids by * nbx + bx) a uint64 whose bit k says record k of `records`
+    ((n, 12) float32 in the device's format, csrc/nh_traverse.h) can be hit by one of the block's camera rays. None when the feature is absent
+    (more than 64 records, or a camera with a lens)."""
+    rec = np.ascontiguousarray(records, dtype=np.float32).reshape(-1, 12)
+    blk = np.ascontiguousarray(blocks, dtype=np.int32).ravel()
+    out = np.zeros(len(blk), np.uint64)
+    built = _i32(0)
+    _host_check(_lib.nh_primary_masks(C.byref(camera), _fptr(rec), len(rec), blk.ctypes.data_as(C.POINTER(_i32)),
+                                      len(blk), out.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(built)),
+                "primary_masks")
+    return out if built.value else None
 
 
 def reduce_framebuffers(ctxs, root: int = 0):
