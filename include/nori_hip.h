@@ -425,6 +425,11 @@ typedef struct nh_render_stats {
        after a megakernel render) and a wavefront chunk sets it when it starts on a path pool, which for an
        asynchronous call can be after nh_render returns: read it after nh_synchronize. */
     uint64_t primary_masks;
+    /* 1 when the last render's fused bounce / tail kernels tested pair records arranged by kind (nh_pair_layout with
+       by_kind: triangles paired with triangles, spheres with spheres): a wavefront render on the LDS-staged fused
+       kernels without collect_stats, the scene uploaded without NH_PAIR_KINDS=0 (read when the BVH is uploaded). 0: the
+       reference arrangement, records paired in their own order. Cleared and set like primary_masks. */
+    uint64_t pair_kinds;
 } nh_render_stats;
 
 typedef struct nh_scene nh_scene;
@@ -494,6 +499,14 @@ void nh_bvh_free(nh_bvh *bvh);
 int nh_primary_masks(const nh_camera *camera, const float *records, int32_t n_records, const int32_t *blocks,
                      int32_t n_blocks, uint64_t *masks, int32_t *built);
 int32_t nh_primary_mask_pad(int32_t width, int32_t height);
+
+/* Which primitive records share a pair record of a small scene's LDS image (host/gpu_layout.cpp pair_layout; host
+ * only). records: as for nh_primary_masks; leaves: n_leaves (start, count) ranges of records, disjoint. slots: 2 ints per
+ * pair position, n_records positions -- (slot 0 record, slot 1 record or -1), (-1, -1) for an unused position.
+ * leaf_pairs: 3 ints per leaf -- first pair position, triangle pairs, sphere pairs. by_kind != 0: a leaf's triangles
+ * two by two, then its spheres two by two; 0: the reference arrangement, position p = records (p, p + 1), both counts 0. */
+int nh_pair_layout(const float *records, int32_t n_records, const int32_t *leaves, int32_t n_leaves, int32_t by_kind,
+                   int32_t *slots, int32_t *leaf_pairs);
 
 /* ImageBlock::toBitmap (src/utils/block.cpp:76-82): rgbw with border -> W*H*3 rgb */
 int nh_framebuffer_to_rgb(const float *rgbw, int32_t width, int32_t height, int32_t border, float *rgb);

@@ -197,6 +197,12 @@ struct nh_ctx {
     // (all 0: tables not staged)
     float4 *small_image = nullptr;
     int small_tab[5] = {0, 0, 0, 0, 0};
+    // pair_kinds: small_image's pair records are arranged by kind (host/gpu_layout.cpp pair_layout; NH_PAIR_KINDS=0 at
+    // the BVH's upload: the reference arrangement). The counting kernels' any-hit primitive counts depend on the test
+    // order, so a collect_stats render stages small_image_ref, the same image in the reference arrangement (null
+    // without pair_kinds: small_image is that image).
+    bool pair_kinds = false;
+    float4 *small_image_ref = nullptr;
     // Candidate masks of the camera rays' first closest hit (WfLaunch::pmask, host/primary_masks.cpp): built by
     // nh_render (ensure_primary_masks) from the uploaded camera, the primitive records (kept here when there are at
     // most 64) and the pixel list's blocks; every upload and every new pixel list frees them (drop_primary_masks), so

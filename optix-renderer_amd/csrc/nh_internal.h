@@ -191,7 +191,7 @@ struct WfLaunch {
     int small_nodes, small_leaves, small_prims;
     int small_frames;  // 1: the fused kernels also stage the flat triangles' shading frames (Traversal::frames)
     // The LDS image of a small scene, built once per upload (nh_upload.hip build_small_image): float4 regions in this
-    // order -- nodes, primitive records, leaf table, pair records, scene tables, flat-triangle frames -- which the
+    // order -- nodes, primitive records, leaf table, pair records, pair-leaf table, scene tables, flat-triangle frames -- which the
     // fused kernels copy as it stands (stage_small_scene). small_tab: float4 counts of the table regions (shapes,
     // bsdfs, emitters, the emitting meshes' area CDFs, emit_faces), all 0 when the tables are not staged (over
     // kSmallTablesBytes, or a scene the diffuse area-light kernels do not run on): only those kernels read them.
@@ -253,9 +253,10 @@ void launch_wf_tail(const nhd::DScene *S, const nhd::Traversal &tv, const WfLaun
 void launch_wf_pack_rr(const WfLaunch &L, const WfBuf &dst, unsigned *dst_counts, int bound, hipStream_t st);
 // n_copy count words src -> host_dst (pinned, device-visible), then n_zero words of zero cleared (wf_counts_kernel)
 // the computed regions of a small scene's LDS image (pair records at float4 pairs_off, frames at frames_off or none
-// if < 0), from n_prim_f4 / 3 primitive records, by the float operations the kernels' own staging used to run
-void launch_small_image(const nhd::Traversal &tv, int n_prim_f4, int pairs_off, int frames_off, float4 *image,
-                        hipStream_t st);
+// if < 0), from n_prim_f4 / 3 primitive records, by the float operations the kernels' own staging used to run; slots
+// (device): the two records of each pair position (host/gpu_layout.cpp pair_layout)
+void launch_small_image(const nhd::Traversal &tv, int n_prim_f4, const int2 *slots, int pairs_off, int frames_off,
+                        float4 *image, hipStream_t st);
 void launch_wf_counts(const unsigned *src, unsigned *host_dst, int n_copy, unsigned *zero, int n_zero, hipStream_t st);
 }  // namespace nh
 

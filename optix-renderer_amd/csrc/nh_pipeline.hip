@@ -218,7 +218,8 @@ static int pool_start(nh_ctx *c, WfPool &p, const WfJob &job) {
         // normalize + frame construction per hit) while they add little LDS
         L.small_frames = c->n_prim_f4 / 3 <= kSmallFramesMaxPrims;
         if (const char *e = std::getenv("NH_LDS_FRAMES")) L.small_frames = L.small_frames && e[0] != '0';
-        L.small_image = c->small_image;
+        // (the counting kernels' any-hit primitive counts follow the reference's test order: its arrangement)
+        L.small_image = j.stats && c->small_image_ref ? c->small_image_ref : c->small_image;
         for (int i = 0; i < 5; ++i) L.small_tab[i] = c->small_tab[i];
     }
     const int per_chunk = 256;  // wf_shade's chunk
@@ -277,6 +278,7 @@ static int pool_start(nh_ctx *c, WfPool &p, const WfJob &job) {
     L.pmask = masks ? c->pmask : nullptr;
     L.pmask_nbx = c->nbx;
     c->stats.primary_masks = masks ? 1 : 0;
+    c->stats.pair_kinds = p.fused && c->pair_kinds && !j.stats ? 1 : 0;
     c->stats.fused_bounce = p.fused ? 1 : 0;
     c->stats.node_bytes = p.wide ? 16 * nhd::kWideF4 * (c->wide_w / 4) : 64;
     c->stats.lds_scene = small && !p.persistent && c->depth <= 16 ? 1 : 0;  // the SMALL instantiations (DEPTH 16)
@@ -861,6 +863,7 @@ int nh_render(nh_ctx *c, const nh_render_req *q) {
     if (wavefront && (rc = ensure_primary_masks(c))) return rc;
     c->stats.node_bytes = 64;  // binary tree unless a wavefront pool picks the 4-wide one
     c->stats.primary_masks = 0;
+    c->stats.pair_kinds = 0;
     c->stats.trace_fused = 0;
     c->stats.lds_scene = 0;
     c->stats.fused_bounce = 0;

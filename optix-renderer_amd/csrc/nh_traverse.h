@@ -223,14 +223,60 @@ NHD bool sphere_test(float4 a, F3 o, F3 d, float mint, float maxt, float &t) {
     return false;
 }
 
+// Two sphere_test calls at once, one per component: the same operations in the same order, the sums, products and
+// differences in packed FP32 (each component the IEEE result of the scalar operation), sqrt and the divisions per
+// component as written there. Returns both roots of each sphere without the range test (the caller applies
+// sphere_test's, slot 0 first: a hit of slot 0 shrinks maxt for slot 1); ok: discr is not negative. Rays that miss
+// both spheres' discriminant test skip the roots -- a whole wave does when all its lanes do.
+NHD void sphere_test_pair(f2 cx, f2 cy, f2 cz, f2 rad, F3 o, F3 d, f2 &tmin, f2 &tmax, bool &ok0, bool &ok1) {
+    const P3 po{f2{o.x, o.x}, f2{o.y, o.y}, f2{o.z, o.z}}, pd{f2{d.x, d.x}, f2{d.y, d.y}, f2{d.z, d.z}};
+    const P3 L = psub(po, P3{cx, cy, cz});
+    const float qa = dot(d, d);
+    const f2 qb = 2.f * pdot(pd, L);
+    const f2 qc = pdot(L, L) - rad * rad;
+    const f2 discr = qb * qb - (4.f * qa) * qc;
+    ok0 = !(discr.x < 0.f);
+    ok1 = !(discr.y < 0.f);
+    tmin = tmax = f2{0.f, 0.f};
+    if (ok0 | ok1) {
+        const f2 s{f_sqrt(discr.x), f_sqrt(discr.y)};
+        const f2 lo = (-qb - s) / 2, hi = (-qb + s) / 2;
+        tmin = f2{lo.x / qa, lo.y / qa};
+        tmax = f2{hi.x / qa, hi.y / qa};
+    }
+}
+// sphere_test's range test on the two roots: the accepted root in t
+NHD bool sphere_in_range(float tmin, float tmax, float mint, float maxt, float &t) {
+    const bool near_ok = mint <= tmin && maxt >= tmin;
+    t = near_ok ? tmin : tmax;
+    return near_ok || (mint <= tmax && maxt >= tmax);
+}
+
+// A hit at t of record k against the leaf loops' acceptance rule, as selects: it replaces the best on t < maxt or a
+// later record (the caller has tested t <= maxt)
+NHD void accept_hit(bool hit, float t, float u, float v, int k, float &maxt, Hit &best, bool &found) {
+    const bool up = hit && (t < maxt || k > best.k);
+    maxt = up ? t : maxt;
+    best.t = up ? t : best.t;
+    best.u = up ? u : best.u;
+    best.v = up ? v : best.v;
+    best.k = up ? k : best.k;
+    found = found || up;
+}
+
 struct Traversal {
     const float4 *nodes;
     const int2 *leaves;
     const float4 *prims;
     const float4 *wnodes;  // 4-wide collapse of the same tree (kWideF4 float4 per node), see Tracer4
-    // LDS-staged scenes (wf_bounce): records k and k+1 interleaved component by component, kPairF4 float4
-    // per k, so a primitive pair loads straight into packed-FP32 register pairs (leaf_test<.., PAIRS>)
+    // LDS-staged scenes (wf_bounce): two records interleaved component by component, kPairF4 float4 per pair
+    // position, so a primitive pair loads straight into packed-FP32 register pairs (leaf_test<.., PAIRS>). Which two
+    // records a position holds is the host's choice (host/gpu_layout.cpp pair_layout), written into the record; in
+    // the reference arrangement position k holds records k and k+1.
     const float4 *ppairs;
+    // per leaf (first pair position, triangle pairs | sphere pairs << 16) of an arrangement by kind; .y == 0: the
+    // reference arrangement (or an empty leaf)
+    const int2 *pleaves;
     // LDS-staged scenes: each triangle's shading frame when its mesh has no normals (Mesh::setHitInformation's
     // Frame(normalized(cross(p1 - p0, p2 - p0))), mesh.cpp:180-190), 3 float4 (s, t, n) per record, computed at
     // staging by the same arithmetic; nullptr: hit_info computes it
@@ -239,9 +285,11 @@ struct Traversal {
     // them first); the persistent traversal kernels read those from an LDS copy
     int n_top;
 };
-// pair k: (a.x a.x') (a.y a.y') | (a.z a.z') (a.w a.w') | (e1.x e1.x') (e1.y e1.y') | (e1.z e1.z') (e2.x e2.x') |
-//         (e2.y e2.y') (e2.z e2.z') | (c.w c.w') (0 0)   -- unprimed record k, primed record k+1; a = p0 (a sphere's
-//         centre and radius), e1 = p1 - p0, e2 = p2 - p0 (triangles only)
+// pair: (a.x a.x') (a.y a.y') | (a.z a.z') (a.w a.w') | (e1.x e1.x') (e1.y e1.y') | (e1.z e1.z') (e2.x e2.x') |
+//       (e2.y e2.y') (e2.z e2.z') | (c.w c.w') (int k, int k')   -- unprimed the record of slot 0, primed of slot 1, k
+//       and k' their record indices; a = p0 (a sphere's centre and radius), e1 = p1 - p0, e2 = p2 - p0 (triangles
+//       only). A slot 0 without a partner is repeated in slot 1 (k' = k): the repeat yields the same candidate and
+//       loses the tie rule against itself, so it changes no answer.
 constexpr int kPairF4 = 6;
 
 // primitive record bits (word 2 .w of the record): kPrimSphere, kPrimLeafEnd, kPrimMatShift, kPrimIsolated (nh_layout.h)
@@ -256,6 +304,59 @@ NHD int prim_material(float4 c) { return (__float_as_int(c.w) >> kPrimMatShift) 
 template <bool ANY, bool STATS, bool PAIRS = false, bool MASKED = false>
 NHD bool leaf_test(const Traversal &tv, int leaf, F3 o, F3 d, float mint, float &maxt, Hit &best, bool &found,
                    TravStats &st, unsigned long long cand = ~0ull) {
+    if constexpr (PAIRS && !STATS) {
+        // Pair records arranged by kind (Traversal::pleaves): the leaf's triangle pairs, then its sphere pairs, each
+        // record under the index it has in tv.prims (stored in its pair). The answer is the in-order loop's: a record's
+        // candidate t does not depend on maxt (a sphere's is tmin when that is past mint, else tmax), the rule below
+        // accepts a candidate t <= maxt when t < maxt or its record is later than the best's, so after any order of
+        // tests the best is the smallest candidate, ties to the largest record index; any hit is an OR.
+        const int2 pl = tv.pleaves[leaf];
+        if (pl.y) {
+            const float4 *pp = tv.ppairs + (size_t)kPairF4 * pl.x;
+            for (int i = 0, n = pl.y & 0xffff; i < n; ++i, pp += kPairF4) {
+                const float4 q5 = pp[5];
+                const int k0 = __float_as_int(q5.z), k1 = __float_as_int(q5.w);
+                if constexpr (MASKED)
+                    if (!(((cand >> (k0 & 63)) | (cand >> (k1 & 63))) & 1ull)) continue;
+                const float4 q0 = pp[0], q1 = pp[1], q2 = pp[2], q3 = pp[3], q4 = pp[4];
+                const P3 p0{f2{q0.x, q0.y}, f2{q0.z, q0.w}, f2{q1.x, q1.y}};
+                const P3 e1{f2{q2.x, q2.y}, f2{q2.z, q2.w}, f2{q3.x, q3.y}};
+                const P3 e2{f2{q3.z, q3.w}, f2{q4.x, q4.y}, f2{q4.z, q4.w}};
+                f2 pt, pu, pv;
+                bool ok0, ok1;
+                tri_test_pair_e(p0, e1, e2, o, d, mint, pt, pu, pv, ok0, ok1);
+                if (ANY) {
+                    if ((ok0 && pt.x <= maxt) || (ok1 && pt.y <= maxt)) return true;
+                    continue;
+                }
+                accept_hit(ok0 && pt.x <= maxt, pt.x, pu.x, pv.x, k0, maxt, best, found);
+                accept_hit(ok1 && pt.y <= maxt, pt.y, pu.y, pv.y, k1, maxt, best, found);
+            }
+            for (int i = 0, n = pl.y >> 16; i < n; ++i, pp += kPairF4) {
+                const float4 q5 = pp[5];
+                const int k0 = __float_as_int(q5.z), k1 = __float_as_int(q5.w);
+                if constexpr (MASKED)
+                    if (!(((cand >> (k0 & 63)) | (cand >> (k1 & 63))) & 1ull)) continue;
+                const float4 q0 = pp[0], q1 = pp[1];
+                f2 tmin, tmax;
+                bool ok0, ok1;
+                sphere_test_pair(f2{q0.x, q0.y}, f2{q0.z, q0.w}, f2{q1.x, q1.y}, f2{q1.z, q1.w}, o, d, tmin, tmax, ok0, ok1);
+                if (!(ok0 | ok1)) continue;
+                float t0, t1;
+                if (ANY) {
+                    if ((sphere_in_range(tmin.x, tmax.x, mint, maxt, t0) && ok0) ||
+                        (sphere_in_range(tmin.y, tmax.y, mint, maxt, t1) && ok1))
+                        return true;
+                    continue;
+                }
+                const bool h0 = sphere_in_range(tmin.x, tmax.x, mint, maxt, t0) && ok0;
+                accept_hit(h0, t0, 0.f, 0.f, k0, maxt, best, found);
+                const bool h1 = sphere_in_range(tmin.y, tmax.y, mint, maxt, t1) && ok1;
+                accept_hit(h1, t1, 0.f, 0.f, k1, maxt, best, found);
+            }
+            return false;
+        }
+    }
     const int2 lf = tv.leaves[leaf];
     if constexpr (PAIRS) {  // interleaved pair records: no AoS -> pair shuffles
         for (int k = lf.x, e = lf.x + lf.y; k < e; k += 2) {

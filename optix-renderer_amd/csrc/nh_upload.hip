@@ -419,7 +419,8 @@ int nh_upload_scene(nh_ctx *c, const nh_scene_desc *d) {
     c->h_emitters = de;
     c->h_area_cdf.assign(d->area_cdf, d->area_cdf + d->n_area_cdf);
     c->n_emit_faces = (int)ef_tri.size();
-    c->small_image = nullptr;  // (the BVH and its image went with bvh_bufs above)
+    c->small_image = c->small_image_ref = nullptr;  // (the BVH and its images went with bvh_bufs above)
+    c->pair_kinds = false;
     c->V.assign(d->V, d->V + 3 * nv);
     c->F.assign(d->F, d->F + 3 * (size_t)d->n_faces);
     c->width = d->camera.width;
@@ -459,8 +460,11 @@ int nh_upload_scene(nh_ctx *c, const nh_scene_desc *d) {
 // BSDFs, emitters, the emitting meshes' area CDFs packed one after the other (the image's shape records index them)
 // and the emit_faces records. Frames are part of the image whenever the scene is small enough for them; a render
 // that does not want them copies the image without its last region.
-static int build_small_image(nh_ctx *c) {
-    c->small_image = nullptr;
+// The pair records follow the host's pair_layout of g's leaves and records: by kind (NH_PAIR_KINDS=0: the reference
+// arrangement), and then a second image in the reference arrangement for the counting kernels (nh_ctx::small_image_ref).
+static int build_small_image(nh_ctx *c, const nh::GpuBvh &g) {
+    c->small_image = c->small_image_ref = nullptr;
+    c->pair_kinds = false;
     for (int &v : c->small_tab) v = 0;
     const size_t scene_bytes = 16 * (size_t)(c->n_node_f4 + c->n_prim_f4) + 8 * (size_t)c->n_leaves;
     if (scene_bytes > kSmallSceneBytes) return NH_OK;
@@ -503,29 +507,42 @@ static int build_small_image(nh_ctx *c) {
         }
     }
     const int tab_f4 = (int)tab.size() + c->small_tab[4];
-    const int frames_off = pairs_off + nhd::kPairF4 * n + tab_f4;
+    const int pleaves_off = pairs_off + nhd::kPairF4 * n, tab_off = pleaves_off + leaves_f4;
+    const int frames_off = tab_off + tab_f4;
     const size_t total = (size_t)frames_off + (frames ? 3 * (size_t)n : 0);
-    float4 *img = nullptr;
-    HIP_TRY(c, hipMalloc(&img, std::max<size_t>(total, 1) * sizeof(float4)));
-    c->bvh_bufs.push_back(img);
-    HIP_TRY(c, hipMemsetAsync(img, 0, std::max<size_t>(total, 1) * sizeof(float4), c->stream));
     const auto d2d = [&](float4 *dst, const void *src, size_t bytes) {
         return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->stream) : hipSuccess;
     };
-    HIP_TRY(c, d2d(img, c->tv.nodes, 16 * (size_t)c->n_node_f4));
-    HIP_TRY(c, d2d(img + c->n_node_f4, c->tv.prims, 16 * (size_t)c->n_prim_f4));
-    HIP_TRY(c, d2d(img + c->n_node_f4 + c->n_prim_f4, c->tv.leaves, 8 * (size_t)c->n_leaves));
-    if (n > 0) {
-        nh::launch_small_image(c->tv, c->n_prim_f4, pairs_off, frames ? frames_off : -1, img, c->stream);
-        HIP_TRY(c, hipGetLastError());
+    const char *pk = std::getenv("NH_PAIR_KINDS");
+    c->pair_kinds = n > 0 && !(pk && pk[0] == '0');
+    for (int pass = 0; pass < (c->pair_kinds ? 2 : 1); ++pass) {
+        const bool by_kind = c->pair_kinds && pass == 0;
+        const nh::PairLayout pl = nh::pair_layout(g.leaves.data(), c->n_leaves, g.prims.data(), n, by_kind);
+        float4 *img = nullptr;
+        HIP_TRY(c, hipMalloc(&img, std::max<size_t>(total, 1) * sizeof(float4)));
+        c->bvh_bufs.push_back(img);
+        HIP_TRY(c, hipMemsetAsync(img, 0, std::max<size_t>(total, 1) * sizeof(float4), c->stream));
+        HIP_TRY(c, d2d(img, c->tv.nodes, 16 * (size_t)c->n_node_f4));
+        HIP_TRY(c, d2d(img + c->n_node_f4, c->tv.prims, 16 * (size_t)c->n_prim_f4));
+        HIP_TRY(c, d2d(img + c->n_node_f4 + c->n_prim_f4, c->tv.leaves, 8 * (size_t)c->n_leaves));
+        if (n > 0) {
+            const nh::i2 *slots = nullptr;
+            if (int rc = upload(c, c->bvh_bufs, pl.slots.data(), pl.slots.size(), &slots)) return rc;
+            nh::launch_small_image(c->tv, c->n_prim_f4, reinterpret_cast<const int2 *>(slots), pairs_off,
+                                   frames ? frames_off : -1, img, c->stream);
+            HIP_TRY(c, hipGetLastError());
+        }
+        if (c->n_leaves > 0)
+            HIP_TRY(c, hipMemcpyAsync(img + pleaves_off, pl.leaves.data(), 8 * (size_t)c->n_leaves, hipMemcpyHostToDevice,
+                                      c->stream));
+        if (!tab.empty()) {
+            float4 *t = img + tab_off;
+            HIP_TRY(c, hipMemcpyAsync(t, tab.data(), tab.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, d2d(t + tab.size(), c->S.emit_faces, 16 * (size_t)c->small_tab[4]));
+        }
+        HIP_TRY(c, hipStreamSynchronize(c->stream));  // (pl and tab are locals)
+        (pass == 0 ? c->small_image : c->small_image_ref) = img;
     }
-    if (!tab.empty()) {
-        float4 *t = img + pairs_off + nhd::kPairF4 * n;
-        HIP_TRY(c, hipMemcpyAsync(t, tab.data(), tab.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, d2d(t + tab.size(), c->S.emit_faces, 16 * (size_t)c->small_tab[4]));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));  // (tab is a local)
-    }
-    c->small_image = img;
     return NH_OK;
 }
 
@@ -580,7 +597,7 @@ int nh_upload_bvh(nh_ctx *c, const nh_bvh_desc *b) {
     c->depth = (int)g.tree_depth + 2;
     if (!c->d_scene) HIP_TRY(c, hipMalloc(&c->d_scene, sizeof(nhd::DScene)));
     HIP_TRY(c, hipMemcpyAsync(c->d_scene, &c->S, sizeof(nhd::DScene), hipMemcpyHostToDevice, c->stream));
-    if ((rc = build_small_image(c))) return rc;
+    if ((rc = build_small_image(c, g))) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->has_bvh = true;
     return NH_OK;

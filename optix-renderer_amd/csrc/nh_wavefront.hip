@@ -174,32 +174,38 @@ __host__ __device__ __forceinline__ int small_pairs_offset_f4(const WfLaunch &L)
     return L.small_nodes + L.small_prims + (L.small_leaves + 1) / 2;
 }
 
+// float4 count of the pair region: kPairF4 per pair position (one per record), then the pair-leaf table
+// (Traversal::pleaves, an int2 per leaf)
+__host__ __device__ __forceinline__ int small_pairs_f4(const WfLaunch &L) {
+    return kPairF4 * (L.small_prims / 3) + (L.small_leaves + 1) / 2;
+}
+
 // float4 count of the scene tables of a small scene's LDS image (WfLaunch::small_tab)
 __host__ __device__ __forceinline__ int small_tables_f4(const WfLaunch &L) {
     return L.small_tab[0] + L.small_tab[1] + L.small_tab[2] + L.small_tab[3] + L.small_tab[4];
 }
 
-// The computed regions of a small scene's LDS image, written by threads tid, tid + nthreads, ...: the
-// pair-interleaved copy of the n primitive records (Traversal::ppairs, kPairF4 float4 per record; the partner of the
-// last record = zeros) and, with frames != null, the flat triangles' shading frames (hit_info reads them instead of
+// The computed regions of a small scene's LDS image, written by threads tid, tid + nthreads, ...: the n pair
+// positions' interleaved copies of two primitive records each (Traversal::ppairs, kPairF4 float4 per position; slots[p]
+// = the two records of position p, host/gpu_layout.cpp pair_layout: a slot 0 without a partner is repeated, an unused
+// position stays zero) and, with frames != null, the flat triangles' shading frames (hit_info reads them instead of
 // a normalize + frame construction per hit). Run once per upload (small_image_kernel): the fused kernels used to run
 // it once per workgroup.
-__device__ __forceinline__ void build_pairs_frames(const float4 *prims_in, int n, float4 *pairs, float4 *frames, int tid,
-                                                   int nthreads) {
-    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int k = tid; k < n; k += nthreads) {
+__device__ __forceinline__ void build_pairs_frames(const float4 *prims_in, int n, const int2 *slots, float4 *pairs,
+                                                   float4 *frames, int tid, int nthreads) {
+    for (int p = tid; p < n; p += nthreads) {
+        const int k = slots[p].x, k1 = slots[p].y < 0 ? k : slots[p].y;
+        if (k < 0) continue;
         const float4 a = prims_in[3 * k], b = prims_in[3 * k + 1], c = prims_in[3 * k + 2];
-        const bool nx = k + 1 < n;
-        const float4 a1 = nx ? prims_in[3 * k + 3] : z, b1 = nx ? prims_in[3 * k + 4] : z,
-                     c1 = nx ? prims_in[3 * k + 5] : z;
-        float4 *q = pairs + (size_t)kPairF4 * k;
+        const float4 a1 = prims_in[3 * k1], b1 = prims_in[3 * k1 + 1], c1 = prims_in[3 * k1 + 2];
+        float4 *q = pairs + (size_t)kPairF4 * p;
         // Moller-Trumbore's edges (mesh.cpp:105-106), subtracted once here instead of in every test
         q[0] = make_float4(a.x, a1.x, a.y, a1.y);
         q[1] = make_float4(a.z, a1.z, a.w, a1.w);
         q[2] = make_float4(b.x - a.x, b1.x - a1.x, b.y - a.y, b1.y - a1.y);
         q[3] = make_float4(b.z - a.z, b1.z - a1.z, c.x - a.x, c1.x - a1.x);
         q[4] = make_float4(c.y - a.y, c1.y - a1.y, c.z - a.z, c1.z - a1.z);
-        q[5] = make_float4(c.w, c1.w, 0.f, 0.f);
+        q[5] = make_float4(c.w, c1.w, __int_as_float(k), __int_as_float(k1));
     }
     if (frames) {
         for (int k = tid; k < n; k += nthreads) {
@@ -219,7 +225,7 @@ __device__ __forceinline__ void build_pairs_frames(const float4 *prims_in, int n
 // float4 count of the dynamic LDS of the fused kernels = of the LDS image they copy: BVH, pair records, scene tables,
 // and the flat triangles' frames (last: left out with small_frames = 0)
 __host__ __device__ __forceinline__ int rr_lds_f4(const WfLaunch &L) {
-    return small_pairs_offset_f4(L) + kPairF4 * (L.small_prims / 3) + small_tables_f4(L) +
+    return small_pairs_offset_f4(L) + small_pairs_f4(L) + small_tables_f4(L) +
            (L.small_frames ? 3 * (L.small_prims / 3) : 0);
 }
 
@@ -237,6 +243,7 @@ __device__ __forceinline__ Traversal stage_small_scene(const Traversal &tv, cons
     t.prims = prims;
     t.leaves = leaves;
     t.ppairs = nullptr;
+    t.pleaves = nullptr;
     t.frames = nullptr;
     t.wnodes = tv.wnodes;
     t.n_top = 0;
@@ -252,7 +259,8 @@ __device__ __forceinline__ Traversal stage_small_scene(const Traversal &tv, cons
         }
         float4 *pairs = lds + small_pairs_offset_f4(L);
         t.ppairs = pairs;
-        if (L.small_frames) t.frames = pairs + kPairF4 * (L.small_prims / 3) + small_tables_f4(L);
+        t.pleaves = reinterpret_cast<const int2 *>(pairs + kPairF4 * (L.small_prims / 3));
+        if (L.small_frames) t.frames = pairs + small_pairs_f4(L) + small_tables_f4(L);
     } else {
         for (int i = threadIdx.x; i < L.small_nodes; i += blockDim.x) nodes[i] = tv.nodes[i];
         for (int i = threadIdx.x; i < L.small_prims; i += blockDim.x) prims[i] = tv.prims[i];
@@ -273,7 +281,7 @@ struct SceneTables {
     const float4 *emit_faces;
 };
 __device__ __forceinline__ SceneTables staged_tables(const WfLaunch &L, float4 *lds) {
-    float4 *p = lds + small_pairs_offset_f4(L) + kPairF4 * (L.small_prims / 3);
+    float4 *p = lds + small_pairs_offset_f4(L) + small_pairs_f4(L);
     SceneTables T;
     T.shapes = reinterpret_cast<const DShape *>(p);
     p += L.small_tab[0];
@@ -1593,8 +1601,9 @@ __global__ __launch_bounds__(256) void wf_camera_rays(const DScene *__restrict__
 }
 
 // the computed regions of a small scene's LDS image, once per upload (nh_upload.hip build_small_image)
-__global__ __launch_bounds__(256) void small_image_kernel(const float4 *prims, int n, float4 *pairs, float4 *frames) {
-    build_pairs_frames(prims, n, pairs, frames, (int)threadIdx.x, 256);
+__global__ __launch_bounds__(256) void small_image_kernel(const float4 *prims, int n, const int2 *slots, float4 *pairs,
+                                                          float4 *frames) {
+    build_pairs_frames(prims, n, slots, pairs, frames, (int)threadIdx.x, 256);
 }
 
 __global__ __launch_bounds__(256) void wf_pack_rr(WfLaunch L, WfBuf dst, unsigned *dst_counts) {
@@ -1895,8 +1904,9 @@ void launch_wf_counts(const unsigned *src, unsigned *host_dst, int n_copy, unsig
     hipLaunchKernelGGL(wf_counts_kernel, dim3(1), dim3(256), 0, st, src, host_dst, n_copy, zero, n_zero);
 }
 
-void launch_small_image(const Traversal &tv, int n_prim_f4, int pairs_off, int frames_off, float4 *image, hipStream_t st) {
-    hipLaunchKernelGGL(small_image_kernel, dim3(1), dim3(256), 0, st, tv.prims, n_prim_f4 / 3, image + pairs_off,
+void launch_small_image(const Traversal &tv, int n_prim_f4, const int2 *slots, int pairs_off, int frames_off, float4 *image,
+                        hipStream_t st) {
+    hipLaunchKernelGGL(small_image_kernel, dim3(1), dim3(256), 0, st, tv.prims, n_prim_f4 / 3, slots, image + pairs_off,
                        frames_off >= 0 ? image + frames_off : nullptr);
 }
 

@@ -9,6 +9,7 @@
 #include <functional>
 
 #include "../csrc/nh_layout.h"
+#include "nh_host.h"
 
 namespace nh {
 
@@ -577,4 +578,67 @@ int build_gpu_bvh(const nh_bvh_desc &desc, const std::vector<nh_shape> &shapes, 
     return NH_OK;
 }
 
+PairLayout pair_layout(const i2 *leaves, int n_leaves, const f4 *prims, int n_records, bool by_kind) {
+    PairLayout out;
+    out.slots.assign((size_t)n_records, make_int2(-1, -1));
+    out.leaves.resize((size_t)n_leaves);
+    if (!by_kind) {
+        for (int p = 0; p < n_records; ++p) out.slots[(size_t)p] = make_int2(p, p + 1 < n_records ? p + 1 : -1);
+        for (int l = 0; l < n_leaves; ++l) out.leaves[(size_t)l] = make_int2(leaves[l].x, 0);
+        return out;
+    }
+    std::vector<int> kind[2];  // a leaf's triangles / spheres, in record order
+    for (int l = 0; l < n_leaves; ++l) {
+        const int2 lf = leaves[l];
+        kind[0].clear();
+        kind[1].clear();
+        for (int k = lf.x; k < lf.x + lf.y; ++k) {
+            int bits;
+            std::memcpy(&bits, &prims[3 * (size_t)k + 2].w, 4);
+            kind[bits & nhd::kPrimSphere ? 1 : 0].push_back(k);
+        }
+        // (pairs never outnumber records: ceil(t / 2) + ceil(s / 2) <= t + s, so the positions stay inside the leaf's own)
+        int p = lf.x;
+        for (const std::vector<int> &v : kind)
+            for (size_t i = 0; i < v.size(); i += 2) out.slots[(size_t)p++] = make_int2(v[i], i + 1 < v.size() ? v[i + 1] : -1);
+        const int n_tri = ((int)kind[0].size() + 1) / 2, n_sph = ((int)kind[1].size() + 1) / 2;
+        out.leaves[(size_t)l] = make_int2(lf.x, n_tri | (n_sph << 16));
+    }
+    return out;
+}
+
 }  // namespace nh
+
+extern "C" {
+
+int nh_pair_layout(const float *records, int32_t n_records, const int32_t *leaves, int32_t n_leaves, int32_t by_kind,
+                   int32_t *slots, int32_t *leaf_pairs) {
+    bool ok = n_records >= 0 && n_leaves >= 0 && (n_records == 0 || (records && slots)) &&
+              (n_leaves == 0 || (leaves && leaf_pairs));
+    // the leaves' ranges: inside the records, no record in two leaves, fewer than 2^15 pairs of a kind
+    std::vector<char> used((size_t)std::max(n_records, 0), 0);
+    for (int l = 0; ok && l < n_leaves; ++l) {
+        const int64_t s = leaves[2 * l], n = leaves[2 * l + 1];
+        ok = s >= 0 && n >= 0 && n < 65535 && s + n <= n_records;
+        for (int64_t k = s; ok && k < s + n; ++k) {
+            ok = !used[(size_t)k];
+            used[(size_t)k] = 1;
+        }
+    }
+    if (!ok) {
+        nh::set_host_error("nh_pair_layout: invalid argument");
+        return NH_ERR_INVALID;
+    }
+    static_assert(sizeof(nh::f4) == 4 * sizeof(float) && sizeof(nh::i2) == 2 * sizeof(int32_t), "plain arrays");
+    const nh::PairLayout pl = nh::pair_layout(reinterpret_cast<const nh::i2 *>(leaves), n_leaves,
+                                              reinterpret_cast<const nh::f4 *>(records), n_records, by_kind != 0);
+    if (n_records > 0) std::memcpy(slots, pl.slots.data(), (size_t)n_records * sizeof(nh::i2));
+    for (int l = 0; l < n_leaves; ++l) {
+        leaf_pairs[3 * l] = pl.leaves[(size_t)l].x;
+        leaf_pairs[3 * l + 1] = pl.leaves[(size_t)l].y & 0xffff;
+        leaf_pairs[3 * l + 2] = pl.leaves[(size_t)l].y >> 16;
+    }
+    return NH_OK;
+}
+
+}  // extern "C"

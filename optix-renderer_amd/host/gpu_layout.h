@@ -68,4 +68,18 @@ bool primary_masks(const nh_camera &cam, const f4 *prims, int n_records, const i
 // the pad in pixels a block's rectangle is grown by: at least 2, a 256th of the larger image side
 int primary_mask_pad(int width, int height);
 
+// Which records share a pair record of a small scene's LDS image (csrc/nh_traverse.h leaf_test<.., PAIRS>). There are
+// as many pair positions as records; a leaf's pairs start at the position of its first record.
+//   slots[p]  = (slot 0 record, slot 1 record or -1: slot 0 has no partner); (-1, -1): position p is not used
+//   leaves[l] = (first pair position, triangle pairs | sphere pairs << 16)
+// by_kind: each leaf's triangles in record order two by two, then its spheres two by two -- no pair mixes kinds, and a
+// leaf has at most one single triangle and one single sphere (the last of its kind). Otherwise the reference
+// arrangement: position p = records (p, p + 1) for every p, and leaves[l].y = 0, which sends leaf_test to its loop over
+// the leaf's records in order. prims: the n_records primitive records (3 f4 each); the leaves' ranges lie inside
+// [0, n_records) and do not overlap.
+struct PairLayout {
+    std::vector<i2> slots, leaves;
+};
+PairLayout pair_layout(const i2 *leaves, int n_leaves, const f4 *prims, int n_records, bool by_kind);
+
 }  // namespace nh

@@ -204,7 +204,8 @@ class nh_render_stats(C.Structure):
                                   "tail_coop_cycles_shadow", "tail_coop_cycles_closest", "tail_coop_cycles_head",
                                   "tail_coop_bounces", "bounce_cycles_load", "bounce_cycles_body",
                                   "bounce_cycles_shadow", "bounce_cycles_closest", "bounce_cycles_head",
-                                  "bounce_cycles_store", "bounce_bounces", "bounce_traits", "primary_masks")]
+                                  "bounce_cycles_store", "bounce_bounces", "bounce_traits", "primary_masks",
+                                  "pair_kinds")]
 
 
 def _sig(name, res, *args):
@@ -236,6 +237,7 @@ _sig("nh_bvh_free", None, _vp)
 _sig("nh_primary_masks", _i32, C.POINTER(nh_camera), _fp, _i32, C.POINTER(_i32), _i32, C.POINTER(C.c_uint64),
      C.POINTER(_i32))
 _sig("nh_primary_mask_pad", _i32, _i32, _i32)
+_sig("nh_pair_layout", _i32, _fp, _i32, C.POINTER(_i32), _i32, _i32, C.POINTER(_i32), C.POINTER(_i32))
 _sig("nh_framebuffer_to_rgb", _i32, _fp, _i32, _i32, _i32, _fp)
 _sig("nh_write_pfm", _i32, C.c_char_p, _fp, _i32, _i32)
 _sig("nh_image_load_png", _i32, C.c_char_p, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(_i32), C.POINTER(_i32))
@@ -906,6 +908,20 @@ def primary_masks(camera: nh_camera, records: np.ndarray, blocks):
                                       len(blk), out.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(built)),
                 "primary_masks")
     return out if built.value else None
+
+
+def pair_layout(records: np.ndarray, leaves, by_kind: bool = True):
+    """nh_pair_layout: which records ((n, 12) float32, the device's format) share a pair record of a small scene's LDS
+    image, for the leaf table `leaves` ((start, count) rows). Returns (slots, leaf_pairs): slots (n, 2) int32 per pair
+    position -- (slot 0 record, slot 1 record or -1), (-1, -1) unused -- and leaf_pairs (n_leaves, 3) int32 -- first
+    pair position, triangle pairs, sphere pairs. by_kind False: the reference arrangement."""
+    rec = np.ascontiguousarray(records, dtype=np.float32).reshape(-1, 12)
+    lv = np.ascontiguousarray(leaves, dtype=np.int32).reshape(-1, 2)
+    slots, lp = np.zeros((len(rec), 2), np.int32), np.zeros((len(lv), 3), np.int32)
+    ip = C.POINTER(_i32)
+    _host_check(_lib.nh_pair_layout(_fptr(rec), len(rec), lv.ctypes.data_as(ip), len(lv), 1 if by_kind else 0,
+                                    slots.ctypes.data_as(ip), lp.ctypes.data_as(ip)), "pair_layout")
+    return slots, lp
 
 
 def reduce_framebuffers(ctxs, root: int = 0):
