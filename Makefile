@@ -25,7 +25,7 @@ HOST_SRC := $(PKG)/host/xml_lite.cpp $(PKG)/host/scene_loader.cpp $(PKG)/host/bv
             $(PKG)/host/photon_host.cpp $(PKG)/host/primary_masks.cpp
 HIP_SRC  := $(PKG)/csrc/nh_kernels.hip $(PKG)/csrc/nh_denoise.hip $(PKG)/csrc/nh_splat.hip $(PKG)/csrc/nh_api.hip \
             $(PKG)/csrc/nh_upload.hip $(PKG)/csrc/nh_pipeline.hip $(PKG)/csrc/nh_adaptive_api.hip $(PKG)/csrc/nh_query_api.hip \
-            $(PKG)/csrc/nh_photon_api.hip
+            $(PKG)/csrc/nh_photon_api.hip $(PKG)/csrc/nh_av.hip
 HOST_OBJ := $(patsubst $(PKG)/host/%.cpp,$(OBJDIR)/host_%.o,$(HOST_SRC))
 # nh_wavefront.hip is compiled as five translation units (-DNH_WF_PART=k, each instantiating its own kernels) so
 # its kernels build in parallel

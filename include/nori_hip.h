@@ -67,7 +67,11 @@ enum { NH_INTEGRATOR_PATH_MIS = 0, NH_INTEGRATOR_PATH_MATS = 1, NH_INTEGRATOR_DI
           with a participating medium or a shape without a BSDF */
        NH_INTEGRATOR_PATH_VOL_MATS = 7, NH_INTEGRATOR_PATH_VOL_MIS = 8,
        /* the photon mapper (photonmapper.cpp): renders once nh_photon_map_build has built the context's photon map */
-       NH_INTEGRATOR_PHOTONMAPPER = 9 };
+       NH_INTEGRATOR_PHOTONMAPPER = 9,
+       /* ambient occlusion (av.cpp: one occlusion ray of length nh_av_params::length per camera hit; renders once
+          nh_set_av_params has given the context that length) and the environment map's pdf / 100
+          (EnvMapTester.cpp: needs an environment map) */
+       NH_INTEGRATOR_AV = 10, NH_INTEGRATOR_ENVMAPTESTER = 11 };
 
 /* One Nori Shape (src/shapes/mesh.cpp, src/shapes/sphere.cpp). Mesh data lives in
  * the scene-wide concatenated arrays at the given offsets. */
@@ -474,6 +478,14 @@ typedef struct nh_photon_params {
 } nh_photon_params;
 int nh_scene_get_photon_params(const nh_scene *scene, nh_photon_params *out);
 int nh_scene_set_photon_params(nh_scene *scene, const nh_photon_params *params);
+/* <integrator type="av"> (src/integrators/av.cpp:10-13): `length`, the occlusion ray's maxt. It has no default (the
+ * loader refuses a scene without it). Kept beside nh_scene_desc, like nh_photon_params. On a scene with another
+ * integrator get returns 0. set takes any length that is not NaN. */
+typedef struct nh_av_params {
+    float length;
+} nh_av_params;
+int nh_scene_get_av_params(const nh_scene *scene, nh_av_params *out);
+int nh_scene_set_av_params(nh_scene *scene, const nh_av_params *params);
 /* PhotonData::initialize (src/utils/photon.cpp:30-41): the five 256-entry decode tables, built with std::cos /
  * std::sin / std::ldexp on float as there; exp_table[0] = 0. Host only. */
 int nh_photon_tables(float *cos_theta, float *sin_theta, float *cos_phi, float *sin_phi, float *exp_table);
@@ -730,6 +742,13 @@ int nh_get_photons(nh_ctx *ctx, int32_t first, int32_t n, float *position, float
  *                           deposit index) order, the order of the render's gather). bytes is not written. Needs a map. */
 enum { NH_PHOTON_QUERY_CODEC = 0, NH_PHOTON_QUERY_GATHER = 1 };
 int nh_photon_query(nh_ctx *ctx, int32_t mode, int32_t n, const float *in, uint8_t *bytes, int32_t *count, float *out);
+
+/* ---- the av integrator (src/integrators/av.cpp) ------------------------------------------ */
+
+/* The occlusion ray's length of an NH_INTEGRATOR_AV scene, which nh_scene_desc does not carry. Called after
+ * nh_upload_scene (every scene upload forgets it); nh_render, nh_radiance_query and nh_ttest_scene of an av scene
+ * return NH_ERR_STATE until it has been. NH_ERR_INVALID: a NaN length. */
+int nh_set_av_params(nh_ctx *ctx, const nh_av_params *params);
 
 const char *nh_last_error(const nh_ctx *ctx);
 

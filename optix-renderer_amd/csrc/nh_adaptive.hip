@@ -223,6 +223,8 @@ __global__ __launch_bounds__(64, 2) void ad_path_kernel(const DScene *__restrict
         case 6: li = li_normals<DEPTH, false, false>(S, tv, o, d, mint, maxt, sk, 64, st, queries); break;
         case 7: li = li_path_vol<DEPTH, false, false>(S, tv, rng, o, d, mint, maxt, sk, 64, st, queries); break;
         case 8: li = li_path_vol<DEPTH, false, true>(S, tv, rng, o, d, mint, maxt, sk, 64, st, queries); break;
+        case 10: li = li_av<DEPTH, false, false>(S, tv, rng, o, d, mint, maxt, sk, 64, st, queries); break;
+        case 11: li = li_envmaptester(S, d); break;
         default: li = li_path_mis<DEPTH, false, false>(S, tv, rng, o, d, mint, maxt, sk, 64, st, queries); break;
     }
     A.rad[gid] = make_float4(li.x, li.y, li.z, 0.f);

@@ -84,6 +84,7 @@ void nh_destroy(nh_ctx *c) {
     (void)hipFree(c->pmask);
     (void)hipFree(c->block_rank);
     (void)hipFree(c->staging);
+    free_all(c->av_bufs);
     (void)hipFree(c->counters);
     photon_release(c, true);  // (clears the map's record in d_scene: before d_scene goes)
     (void)hipFree(c->d_scene);

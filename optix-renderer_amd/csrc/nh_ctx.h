@@ -187,6 +187,13 @@ struct nh_ctx {
     int sampler = 0, adaptive_initial_uniform = 0;  // NH_SAMPLER_*; an adaptive scene renders through render_adaptive
     AdaptiveState ad;
     PhotonState photon;
+    bool av_set = false;  // nh_set_av_params since the scene's upload (S.av_length)
+    // chunk buffers of the av integrator's split pipeline (nh_pipeline.hip av_reserve): arrays of av_cap paths
+    AvLaunch av{};
+    std::vector<void *> av_bufs;
+    size_t av_cap = 0;
+    int2 *av_spill = nullptr;  // the wide traversal's per-ray spill area, av_spill_depth entries per path
+    int av_spill_depth = 0;
     // host copies of the scene tables and the emit_faces count, for the LDS image of a small scene (build_small_image)
     std::vector<nhd::DShape> h_shapes;
     std::vector<nhd::DBsdf> h_bsdfs;

@@ -289,7 +289,7 @@ struct DScene {
     const DEmitter *emitters;
     const float *emitter_cdf;
     int n_emitters;
-    int integrator;  // 0 path_mis, 1 path_mats, 2-5 the direct integrators, 6 normals
+    int integrator;  // NH_INTEGRATOR_*
     float ndir[3];   // normals: its `direction`
     const float *V, *N, *UV, *T, *BT;
     const uint32_t *F;
@@ -346,6 +346,8 @@ struct DScene {
     // the photon mapper's map (nh_photon.h; read by li_photonmapper and the gather query alone): all zero until
     // nh_photon_map_build
     DPhotonMap pm;
+    // the av integrator's `length`, the occlusion ray's maxt (nh_set_av_params)
+    float av_length;
 };
 
 NHD F3 ldv(const float *a, uint32_t i) { return f3(a[3 * i], a[3 * i + 1], a[3 * i + 2]); }

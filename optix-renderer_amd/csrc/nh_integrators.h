@@ -5,6 +5,7 @@
 //   li_path_mis / li_path_mats        PathMISIntegrator::Li / PathMatsIntegrator::Li
 //   li_direct_{ems,mats,mis,simple}   the single-bounce direct integrators
 //   li_normals                        NormalIntegrator::Li
+//   li_av / li_envmaptester           AverageVisibilityIntegrator::Li / EnvMapTester::Li
 //
 // With -DNH_DISNEY the functions are nh_disney's, as the kernels that call them are (nh_internal.h).
 #pragma once
@@ -357,6 +358,46 @@ __device__ F3 li_normals(const DScene &S, const Traversal &tv, F3 o, F3 d, float
     hit_info(S, tv, h, o, d, its);
     const F3 n = to_world(its.sh, f3(S.ndir[0], S.ndir[1], S.ndir[2]));
     return f3(fabsf(n.x), fabsf(n.y), fabsf(n.z));
+}
+
+// Warp::sampleUniformHemisphere(sampler, pole) (warp.cpp:25-39): rejection from the cube, three draws per try, the
+// accepted point mirrored into the pole's hemisphere and divided by its norm. squaredNorm and dot in Eigen's grouping
+// (nh_device.h dot); `v /= v.norm()` divides each component by sqrt(squaredNorm). A point at the origin leaves NaN
+// there and here.
+__device__ __forceinline__ F3 av_sample_hemisphere(Rng &rng, F3 pole) {
+    F3 v;
+    do {
+        v.x = 1.f - 2.f * rng.next1d();
+        v.y = 1.f - 2.f * rng.next1d();
+        v.z = 1.f - 2.f * rng.next1d();
+    } while (dot(v, v) > 1.f);
+    if (dot(v, pole) < 0.f) v = neg(v);
+    return divs(v, f_sqrt(dot(v, v)));
+}
+
+// AverageVisibilityIntegrator::Li (src/integrators/av.cpp:18-43): 1 for a camera ray that escapes; otherwise one
+// occlusion ray Ray3f(its.p, dir, Epsilon, length) along a uniform direction of the shading normal's hemisphere, 0 if it
+// hits, 1 if not. The reference asks for that ray's closest hit and reads only whether there is one: the any-hit
+// traversal tests the same primitives against the same [mint, maxt] and returns that boolean.
+template <int DEPTH, bool ORDERED, bool STATS>
+__device__ F3 li_av(const DScene &S, const Traversal &tv, Rng &rng, F3 o, F3 d, float mint, float maxt, uint32_t *stk,
+                    int stride, TravStats &st, uint32_t &queries) {
+    Hit h;
+    if (STATS) queries++;
+    if (!trace<DEPTH, ORDERED, false, STATS>(tv, S, o, d, mint, maxt, h, stk, stride, st)) return f3(1, 1, 1);
+    Its its;
+    hit_info(S, tv, h, o, d, its);
+    const F3 dir = av_sample_hemisphere(rng, its.sh.n);
+    Hit hs;
+    if (STATS) queries++;
+    const float v = trace<DEPTH, ORDERED, true, STATS>(tv, S, its.p, dir, kEps, S.av_length, hs, stk, stride, st) ? 0.f : 1.f;
+    return f3(v, v, v);
+}
+
+// EnvMapTester::Li (src/integrators/EnvMapTester.cpp:16-26): EnvMap::pdf of the camera ray's direction, over 100
+__device__ __forceinline__ F3 li_envmaptester(const DScene &S, F3 d) {
+    const float v = env_pdf(S, d) / 100.f;
+    return f3(v, v, v);
 }
 
 #ifdef NH_DISNEY

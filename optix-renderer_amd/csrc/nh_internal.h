@@ -30,6 +30,21 @@ struct PathLaunch {
     float *rec;             // (r, g, b) per (round, list entry); the splat recomputes the pixel jitter (sample_jitter)
     unsigned long long *counters;
 };
+// One chunk of the av integrator's split pipeline (nh_av.hip): n_paths = rounds * n_list paths, path r = round k, list
+// entry i at k * n_list + i like PathLaunch's records. Every array holds n_paths entries.
+struct AvLaunch {
+    int n_paths, n_list, s0;
+    uint64_t seed;
+    const int *pixel_list;
+    float *rec;        // the chunk's sample records
+    float *ray[8];     // camera rays, SoA in RayBatch's order (ox, oy, oz, dx, dy, dz, mint, maxt)
+    HitBatch hit;      // their closest hits
+    uint64_t *rng;     // pcg32 state of the path's stream after the four camera draws (inc follows from the sample)
+    float *q_ray[8];   // the compact occlusion queue, the same order; entries past *q_count are rays with maxt < mint
+    int *q_path;       // path of queue entry j
+    uint8_t *q_hit;    // its any-hit result
+    unsigned *q_count; // entries appended (zero before av_shade)
+};
 // Row pitch (float4) of one (round, block) ImageBlock of (32+2b)^2 pixels in the splat's staging buffer: rows start
 // on 128-B lines, so the merge's 16-pixel row segments (master columns 16a..16a+15 = block columns 0..15 / 16..31)
 // read whole lines instead of straddling three (the unpadded 36-float4 rows start 64 B off a line every other row)
@@ -126,6 +141,10 @@ void launch_trace_wide(const nhd::DScene *S, const nhd::Traversal &tv, const Ray
 void launch_path(const nhd::DScene *S, const nhd::Traversal &tv, const PathLaunch &L, bool ordered, bool stats,
                  int depth, bool pm, hipStream_t st);
 void launch_splat(const SplatLaunch &P, hipStream_t st);
+// the av integrator's stages around the batch traversals above (nh_av.hip); bound: queue entries to resolve at most
+void launch_av_primary(const nhd::DScene *S, const AvLaunch &L, hipStream_t st);
+void launch_av_shade(const nhd::DScene *S, const nhd::Traversal &tv, const AvLaunch &L, hipStream_t st);
+void launch_av_resolve(const AvLaunch &L, int bound, hipStream_t st);
 // false: launch_splat adds the records straight into the master (no per-(round, block) staging buffer)
 bool splat_uses_staging(int border, int reach);
 void launch_count_invalid(const float *rec, size_t n, unsigned long long *out, hipStream_t st);

@@ -105,6 +105,8 @@ __global__ __launch_bounds__(BLOCK, MINW) void nh_path_kernel(const DScene *__re
             case 4: li = li_direct_mis<DEPTH, ORDERED, STATS>(S, tv, rng, o, d, mint, maxt, stk + threadIdx.x, BLOCK, st, queries); break;
             case 5: li = li_direct_simple<DEPTH, ORDERED, STATS>(S, tv, rng, o, d, mint, maxt, stk + threadIdx.x, BLOCK, st, queries); break;
             case 6: li = li_normals<DEPTH, ORDERED, STATS>(S, tv, o, d, mint, maxt, stk + threadIdx.x, BLOCK, st, queries); break;
+            case 10: li = li_av<DEPTH, ORDERED, STATS>(S, tv, rng, o, d, mint, maxt, stk + threadIdx.x, BLOCK, st, queries); break;
+            case 11: li = li_envmaptester(S, d); break;
             default: li = li_path_mis<DEPTH, ORDERED, STATS>(S, tv, rng, o, d, mint, maxt, stk + threadIdx.x, BLOCK, st, queries); break;
         }
         const size_t r = (size_t)k * L.n_list + i;

@@ -816,6 +816,91 @@ static int ensure_primary_masks(nh_ctx *c) {
     return NH_OK;
 }
 
+// ---- the av integrator's split pipeline (nh_av.hip) ----
+// device bytes per path of a chunk: camera ray and queue ray (32 each), closest hit (17), stream state (8), queue path
+// index (4), any-hit result (1)
+constexpr size_t kAvBytesPerPath = 94;
+
+// The wide tree walks the chunk's batches when a wavefront pool would pick it for the same request (pool_start: a
+// deep tree, a near-first request); every order returns the same hits.
+static bool av_wide(const nh_ctx *c, const nh_render_req *q) {
+    return q->traversal != NH_TRAVERSAL_REFERENCE && c->depth > 20 && c->tv.wnodes != nullptr;
+}
+static size_t av_bytes_per_path(const nh_ctx *c, const nh_render_req *q) {
+    return kAvBytesPerPath + (av_wide(c, q) ? (size_t)c->depth_wide * sizeof(int2) : 0);
+}
+
+// the chunk buffers, kept by the context for the next chunk of at most `paths` paths
+static int av_reserve(nh_ctx *c, size_t paths, bool wide) {
+    const int spill_depth = wide ? c->depth_wide : 0;
+    if (c->av_cap >= paths && c->av_spill_depth >= spill_depth) return NH_OK;
+    free_all(c->av_bufs);
+    c->av_cap = 0;
+    c->av_spill_depth = 0;
+    c->av_spill = nullptr;
+    AvLaunch &L = c->av;
+    L = AvLaunch{};
+    const auto get = [&](auto **p, size_t n) -> int {
+        void *d = nullptr;
+        HIP_TRY(c, hipMalloc(&d, std::max<size_t>(n, 1) * sizeof(**p)));
+        c->av_bufs.push_back(d);
+        *p = static_cast<std::remove_reference_t<decltype(*p)>>(d);
+        return NH_OK;
+    };
+    int rc = NH_OK;
+    for (int i = 0; i < 8 && !rc; ++i)
+        if (!(rc = get(&L.ray[i], paths))) rc = get(&L.q_ray[i], paths);
+    if (rc || (rc = get(&L.hit.hit, paths)) || (rc = get(&L.hit.t, paths)) || (rc = get(&L.hit.u, paths)) ||
+        (rc = get(&L.hit.v, paths)) || (rc = get(&L.hit.k, paths)) || (rc = get(&L.rng, paths)) ||
+        (rc = get(&L.q_path, paths)) || (rc = get(&L.q_hit, paths)) || (rc = get(&L.q_count, 1)) ||
+        (spill_depth && (rc = get(&c->av_spill, paths * (size_t)spill_depth)))) {
+        free_all(c->av_bufs);
+        return rc;
+    }
+    c->av_cap = paths;
+    c->av_spill_depth = spill_depth;
+    return NH_OK;
+}
+
+// One chunk's paths through the stages, on the context's stream: what launch_path does for the megakernel, into the
+// same sample records. Only a render that collects statistics reads the queue's length back (its any-hit launch then
+// covers exactly the queue, so the padding is not counted as queries).
+static int av_chunk(nh_ctx *c, const nh_render_req *q, const PathLaunch &P) {
+    AvLaunch L = c->av;
+    L.n_paths = P.n_paths;
+    L.n_list = P.n_list;
+    L.s0 = P.s0;
+    L.seed = P.seed;
+    L.pixel_list = P.pixel_list;
+    L.rec = P.rec;
+    const bool wide = av_wide(c, q), ordered = q->traversal != NH_TRAVERSAL_REFERENCE, stats = q->collect_stats != 0;
+    const auto batch = [&](float *const r[8], const HitBatch &hb, int n, bool any) {
+        const RayBatch rb{r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7]};
+        // the any-hit work goes to the counters' any-hit share, as the wavefront pools' shadow rays do
+        unsigned long long *ctr = c->counters + (any ? kStatAny : 0);
+        if (wide) nh::launch_trace_wide(c->d_scene, c->tv, rb, hb, n, any, true, stats, c->av_spill, c->av_spill_depth, ctr,
+                                        c->stream, c->wide_w);
+        else nh::launch_trace(c->d_scene, c->tv, rb, hb, n, any, ordered, stats, c->depth, ctr, c->stream);
+    };
+    HIP_TRY(c, hipMemsetAsync(L.q_count, 0, sizeof(unsigned), c->stream));
+    nh::launch_av_primary(c->d_scene, L, c->stream);
+    batch(L.ray, L.hit, L.n_paths, false);
+    nh::launch_av_shade(c->d_scene, c->tv, L, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    int n_queue = L.n_paths;
+    if (stats) {
+        unsigned n = 0;
+        HIP_TRY(c, hipMemcpyAsync(&n, L.q_count, sizeof(n), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        n_queue = (int)n;
+    }
+    HitBatch occl{};
+    occl.hit = L.q_hit;
+    batch(L.q_ray, occl, n_queue, true);
+    nh::launch_av_resolve(L, n_queue, c->stream);
+    return NH_OK;
+}
+
 extern "C" {
 
 int nh_render(nh_ctx *c, const nh_render_req *q) {
@@ -843,6 +928,13 @@ int nh_render(nh_ctx *c, const nh_render_req *q) {
         return fail(c, "nh_render: the photon mapper needs a photon map (nh_photon_map_build)"), NH_ERR_STATE;
     if (photon && c->sampler == NH_SAMPLER_ADAPTIVE)
         return fail(c, "photonmapper: the adaptive sampler is not supported"), NH_ERR_UNSUPPORTED;
+    if (c->integrator == NH_INTEGRATOR_AV && !c->av_set)
+        return fail(c, "nh_render: the av integrator needs its length (nh_set_av_params)"), NH_ERR_STATE;
+    if (c->integrator == NH_INTEGRATOR_ENVMAPTESTER && c->S.envmap < 0)  // EnvMapTester.cpp:19-23
+        return fail(c, "This integrator requires an env map."), NH_ERR_INVALID;
+    // av in wavefront mode: its own split pipeline over the megakernel's chunks (nh_av.hip), the camera paths that
+    // escape leaving before the occlusion query. envmaptester traces nothing: the megakernel, like the direct ones
+    const bool av_split = q->mode == NH_MODE_WAVEFRONT && c->integrator == NH_INTEGRATOR_AV;
     // the single-bounce direct integrators always run as the megakernel: one closest hit, the light
     // sample(s) and at most one BSDF ray per path leave no bounce loop for path queues to balance. The volumetric
     // path tracers have no wavefront version yet: a wavefront request runs their megakernel (nh_volume.hip)
@@ -862,6 +954,7 @@ int nh_render(nh_ctx *c, const nh_render_req *q) {
     if (rc) return rc;
     if (wavefront && (rc = ensure_primary_masks(c))) return rc;
     c->stats.node_bytes = 64;  // binary tree unless a wavefront pool picks the 4-wide one
+    if (av_split && av_wide(c, q)) c->stats.node_bytes = 16 * nhd::kWideF4 * (c->wide_w / 4);
     c->stats.primary_masks = 0;
     c->stats.pair_kinds = 0;
     c->stats.trace_fused = 0;
@@ -880,7 +973,8 @@ int nh_render(nh_ctx *c, const nh_render_req *q) {
     const char *jv = std::getenv("NH_SPLAT_JITTER");  // stored jitter (A/B): 8 more bytes per sample record
     const size_t rec_bytes = kRecFloats * 4 + (wavefront && jv && std::strcmp(jv, "stored") == 0 ? 8 : 0);
     const size_t per_round_bytes = per_round * rec_bytes + (size_t)c->px.n_blocks * block_px(c, splat_staged(c)) * 16 +
-                                   (wavefront ? per_round * kWfBytesPerPath : 0);
+                                   (wavefront ? per_round * kWfBytesPerPath : 0) +
+                                   (av_split ? per_round * av_bytes_per_path(c, q) : 0);
     // device memory per chunk: sample records + block ImageBlocks (+ path state, per pool). Every
     // wavefront chunk ends in a tail whose length is set by its longest path (C4: ~5-7 ms of
     // dielectric / mirror chains, whatever the chunk's size), so chunks are as large as the 26-bit
@@ -930,6 +1024,7 @@ int nh_render(nh_ctx *c, const nh_render_req *q) {
             HIP_TRY(c, hipMalloc(&c->rec, cap * kRecFloats * sizeof(float)));
             c->rec_cap = cap;
         }
+        if (av_split && (rc = av_reserve(c, (size_t)chunk * per_round, av_wide(c, q)))) return rc;
         const bool staged = splat_staged(c);
         if (c->staging_cap < (size_t)chunk * c->px.n_blocks * block_px(c, staged)) {
             (void)hipFree(c->staging);
@@ -958,7 +1053,9 @@ int nh_render(nh_ctx *c, const nh_render_req *q) {
             HIP_TRY(c, hipEventCreate(&ev.b));
             HIP_TRY(c, hipEventCreate(&ev.d));
             HIP_TRY(c, hipEventRecord(ev.a, c->stream));
-            if (photon)
+            if (av_split) {
+                if ((rc = av_chunk(c, q, L))) return rc;
+            } else if (photon)
                 nh_disney::nh::launch_photon_path(c->d_scene, c->tv, L, q->collect_stats != 0, c->depth, c->stream);
             else if (volumetric)
                 nh_disney::nh::launch_vol_path(c->d_scene, c->tv, L, c->integrator == NH_INTEGRATOR_PATH_VOL_MIS,

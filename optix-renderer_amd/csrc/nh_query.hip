@@ -76,6 +76,8 @@ __global__ __launch_bounds__(64, 2) void path_query_kernel(const DScene *__restr
         case 7: li = li_path_vol<DEPTH, false, false>(S, tv, rng, o, d, mint, maxt, sk, 64, st, queries); break;
         case 8: li = li_path_vol<DEPTH, false, true>(S, tv, rng, o, d, mint, maxt, sk, 64, st, queries); break;
         case 9: li = li_photonmapper<DEPTH, false>(S, tv, rng, o, d, mint, maxt, sk, 64, st, queries); break;
+        case 10: li = li_av<DEPTH, true, false>(S, tv, rng, o, d, mint, maxt, sk, 64, st, queries); break;
+        case 11: li = li_envmaptester(S, d); break;
         default: li = li_path_mis<DEPTH, true, false>(S, tv, rng, o, d, mint, maxt, sk, 64, st, queries); break;
     }
     if (ttest) {

@@ -36,6 +36,10 @@ int path_query_ready(nh_ctx *c, const std::string &who) {
                        "path_vol_mis integrators render it"), NH_ERR_UNSUPPORTED;
     if (c->integrator == NH_INTEGRATOR_PHOTONMAPPER && !c->photon.built)
         return fail(c, who + ": the photon mapper needs a photon map (nh_photon_map_build)"), NH_ERR_STATE;
+    if (c->integrator == NH_INTEGRATOR_AV && !c->av_set)
+        return fail(c, who + ": the av integrator needs its length (nh_set_av_params)"), NH_ERR_STATE;
+    if (c->integrator == NH_INTEGRATOR_ENVMAPTESTER && c->S.envmap < 0)  // EnvMapTester.cpp:19-23
+        return fail(c, "This integrator requires an env map."), NH_ERR_INVALID;
     return NH_OK;
 }
 
@@ -269,6 +273,11 @@ int nh_test_run(int device, const char *path, uint64_t seed, nh_test_result *res
                 nh_photon_params pp;
                 nh_scene_get_photon_params(r.scene, &pp);
                 if (int rc = nh_photon_map_build(r.ctx, &pp, 0, 0)) return ctx_fail(rc);
+            }
+            if (sd.integrator == NH_INTEGRATOR_AV) {
+                nh_av_params ap;
+                nh_scene_get_av_params(r.scene, &ap);
+                if (int rc = nh_set_av_params(r.ctx, &ap)) return ctx_fail(rc);
             }
             double mean = 0, variance = 0;
             if (int rc = nh_ttest_scene(r.ctx, seed, 0, td.sample_count, &mean, &variance, nullptr)) return ctx_fail(rc);

@@ -321,9 +321,10 @@ int nh_upload_scene(nh_ctx *c, const nh_scene_desc *d) {
     }
     S.n_emitters = (int)d->n_emitters;
     S.nee_finite = nh::nee_finite(d) ? 1 : 0;
-    if (d->integrator < NH_INTEGRATOR_PATH_MIS || d->integrator > NH_INTEGRATOR_PHOTONMAPPER)
+    if (d->integrator < NH_INTEGRATOR_PATH_MIS || d->integrator > NH_INTEGRATOR_ENVMAPTESTER)
         return fail(c, "unknown integrator"), NH_ERR_INVALID;
     S.integrator = d->integrator;
+    S.av_length = 0.f;  // nh_set_av_params
     for (int i = 0; i < 3; ++i) S.ndir[i] = d->normals_direction[i];
     std::memcpy(S.s2c, d->camera.sample_to_camera, sizeof(S.s2c));
     std::memcpy(S.c2w, d->camera.camera_to_world, sizeof(S.c2w));
@@ -436,6 +437,7 @@ int nh_upload_scene(nh_ctx *c, const nh_scene_desc *d) {
     c->adaptive_initial_uniform = std::max(1, (int)d->adaptive_initial_uniform);
     adaptive_release(c);  // block samplers of an earlier scene
     photon_release(c);    // and its photon map
+    c->av_set = false;    // and its av length
 
     // master ImageBlock
     (void)hipFree(c->fb);
@@ -543,6 +545,22 @@ static int build_small_image(nh_ctx *c, const nh::GpuBvh &g) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));  // (pl and tab are locals)
         (pass == 0 ? c->small_image : c->small_image_ref) = img;
     }
+    return NH_OK;
+}
+
+int nh_set_av_params(nh_ctx *c, const nh_av_params *params) {
+    if (!c) return NH_ERR_INVALID;
+    if (!params || std::isnan(params->length)) return fail(c, "nh_set_av_params: invalid av parameters"), NH_ERR_INVALID;
+    if (!c->has_scene) return fail(c, "nh_set_av_params: no scene uploaded"), NH_ERR_STATE;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = pipeline_drain(c)) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // kernels in flight read the device copy
+    c->S.av_length = params->length;
+    // the device copy exists once a BVH is uploaded (nh_upload_bvh copies the whole record)
+    if (c->d_scene && c->has_bvh)
+        HIP_TRY(c, hipMemcpy(reinterpret_cast<char *>(c->d_scene) + offsetof(nhd::DScene, av_length), &c->S.av_length,
+                             sizeof(float), hipMemcpyHostToDevice));
+    c->av_set = true;
     return NH_OK;
 }
 

@@ -111,6 +111,11 @@ int main(int argc, char **argv) {
         nh_get_photon_stats(ctx, &ps);
         std::printf("Emitted %d Photons.\n", ps.emitted);
     }
+    if (desc.integrator == NH_INTEGRATOR_AV) {  // the occlusion ray's length travels beside the descriptor
+        nh_av_params ap;
+        nh_scene_get_av_params(scene, &ap);
+        if (nh_set_av_params(ctx, &ap)) return die("av", nh_last_error(ctx));
+    }
     nh_render_req req;
     std::memset(&req, 0, sizeof(req));
     req.sample_begin = 0;

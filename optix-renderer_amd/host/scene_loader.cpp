@@ -223,6 +223,7 @@ struct SceneData {
     // PhotonMapper's properties (photonmapper.cpp:39-40); photon_radius 0 = automatic (nh_scene_get_photon_params)
     int32_t photon_count = 1000000;
     float photon_radius = 0.f;
+    float av_length = 0.f;  // AverageVisibilityIntegrator's `length` (av.cpp:12)
     std::vector<nh_shape> shapes;
     std::vector<nh_bsdf> bsdfs;
     std::vector<nh_emitter> emitters;
@@ -1027,6 +1028,11 @@ void build_scene(const Obj &scene, const std::string &base_dir, SceneData &sd) {
                 sd.photon_count = ch.props.get_int("photonCount", 1000000);
                 sd.photon_radius = ch.props.get_float("photonRadius", 0.0f);
             }
+            else if (ch.type == "av") {  // AverageVisibilityIntegrator (av.cpp:10-13): getFloat without a default
+                sd.integrator = NH_INTEGRATOR_AV;
+                sd.av_length = ch.props.get_float("length");
+            }
+            else if (ch.type == "envmaptester") sd.integrator = NH_INTEGRATOR_ENVMAPTESTER;  // EnvMapTester.cpp:13
             else throw SceneError("integrator \"" + ch.type + "\" is not supported by the HIP path");
         } else if (ch.tag == "camera") {
             if (have_camera) throw SceneError("there can only be one camera per scene");
@@ -1207,6 +1213,9 @@ void build_scene(const Obj &scene, const std::string &base_dir, SceneData &sd) {
         }
     }
     if (have_integrator && sd.integrator == NH_INTEGRATOR_PHOTONMAPPER) check_photonmapper(sd);
+    // EnvMapTester::Li throws it at the first sample (EnvMapTester.cpp:19-23)
+    if (have_integrator && sd.integrator == NH_INTEGRATOR_ENVMAPTESTER && sd.envmap < 0)
+        throw SceneError("This integrator requires an env map.");
     if (!have_integrator) throw SceneError("No integrator was specified!");
     if (!have_camera) throw SceneError("No camera was specified!");
     if (!sd.emitter_ext.empty()) sd.emitter_ext.resize(sd.emitters.size());  // one entry per emitter
@@ -1540,7 +1549,9 @@ int nh_texture_decode(const uint8_t *rgba8, uint64_t n, int32_t srgb, float *out
 }
 
 int nh_scene_set_integrator(nh_scene *scene, int32_t integrator) {
-    if (!scene || integrator < NH_INTEGRATOR_PATH_MIS || integrator > NH_INTEGRATOR_PATH_VOL_MIS) {
+    // (the photon mapper is set by a scene file alone: its checks run in the loader)
+    if (!scene || integrator < NH_INTEGRATOR_PATH_MIS || integrator > NH_INTEGRATOR_ENVMAPTESTER ||
+        integrator == NH_INTEGRATOR_PHOTONMAPPER) {
         nh::set_host_error("invalid integrator");
         return NH_ERR_INVALID;
     }
@@ -1574,6 +1585,21 @@ int nh_scene_set_photon_params(nh_scene *scene, const nh_photon_params *params) 
     }
     scene->data->photon_count = params->photon_count;
     scene->data->photon_radius = params->photon_radius;
+    return NH_OK;
+}
+
+int nh_scene_get_av_params(const nh_scene *scene, nh_av_params *out) {
+    if (!scene || !out) { nh::set_host_error("null argument"); return NH_ERR_INVALID; }
+    out->length = scene->data->av_length;
+    return NH_OK;
+}
+
+int nh_scene_set_av_params(nh_scene *scene, const nh_av_params *params) {
+    if (!scene || !params || std::isnan(params->length)) {
+        nh::set_host_error("invalid av parameters");
+        return NH_ERR_INVALID;
+    }
+    scene->data->av_length = params->length;
     return NH_OK;
 }
 

@@ -319,6 +319,19 @@ _sig("nh_get_photons", _i32, _vp, _i32, _i32, _fp, _fp, _fp, _u8p, _i32p, _i32p)
 _sig("nh_photon_query", _i32, _vp, _i32, _i32, _fp, _u8p, _i32p, _fp)
 
 
+# ---- the av and envmaptester integrators (av.cpp, EnvMapTester.cpp) ----
+INTEGRATOR_AV, INTEGRATOR_ENVMAPTESTER = 10, 11
+
+
+class nh_av_params(C.Structure):
+    _fields_ = [("length", _f)]
+
+
+_sig("nh_scene_get_av_params", _i32, _vp, C.POINTER(nh_av_params))
+_sig("nh_scene_set_av_params", _i32, _vp, C.POINTER(nh_av_params))
+_sig("nh_set_av_params", _i32, _vp, C.POINTER(nh_av_params))
+
+
 def photon_tables() -> dict:
     """nh_photon_tables: PhotonData's five 256-entry decode tables (photon.cpp:30-41), float32."""
     t = {k: np.zeros(256, np.float32) for k in ("cos_theta", "sin_theta", "cos_phi", "sin_phi", "exp")}
@@ -394,6 +407,17 @@ class Scene:
         p = nh_photon_params()
         _host_check(_lib.nh_scene_get_photon_params(self._h, C.byref(p)), "get_photon_params")
         return int(p.photon_count), float(np.float32(p.photon_radius))
+
+    def av_params(self) -> float:
+        """nh_scene_get_av_params: `length` of the scene's av integrator (0 on a scene with another integrator)."""
+        p = nh_av_params()
+        _host_check(_lib.nh_scene_get_av_params(self._h, C.byref(p)), "get_av_params")
+        return float(np.float32(p.length))
+
+    def set_av_params(self, length: float):
+        """nh_scene_set_av_params: override the av integrator's `length`."""
+        p = nh_av_params(length)
+        _host_check(_lib.nh_scene_set_av_params(self._h, C.byref(p)), "set_av_params")
 
     def set_photon_params(self, photon_count: int, photon_radius: float = 0.0):
         """nh_scene_set_photon_params: override photonCount and photonRadius (0 = automatic)."""
@@ -629,9 +653,10 @@ class Context:
         if rc != NH_OK:
             raise NoriError(f"{what}: {_lib.nh_last_error(self._h).decode()} (rc={rc})")
 
-    def upload(self, scene: Scene, bvh: Bvh, photon_map: bool = True):
+    def upload(self, scene: Scene, bvh: Bvh, photon_map: bool = True, av_params: bool = True):
         """Uploads the scene and its BVH; a photon-mapper scene also builds its photon map with seed 0 (photon_map=False
-        leaves that to build_photon_map)."""
+        leaves that to build_photon_map), an av scene also passes its `length` (av_params=False leaves that to
+        set_av_params)."""
         self.scene = scene
         d = scene.desc
         self._check(_lib.nh_upload_scene(self._h, C.byref(d)), "upload_scene")
@@ -639,6 +664,13 @@ class Context:
         self._check(_lib.nh_upload_bvh(self._h, C.byref(b)), "upload_bvh")
         if photon_map and d.integrator == INTEGRATOR_PHOTONMAPPER:  # Integrator::preprocess, map seed 0
             self.build_photon_map(seed=0)
+        if av_params and d.integrator == INTEGRATOR_AV:
+            self.set_av_params()
+
+    def set_av_params(self, length: float = None):
+        """nh_set_av_params on the uploaded scene: the av integrator's occlusion-ray length, the scene's by default."""
+        p = nh_av_params(self.scene.av_params() if length is None else length)
+        self._check(_lib.nh_set_av_params(self._h, C.byref(p)), "set_av_params")
 
     def build_photon_map(self, seed: int = 0, batch_paths: int = 0, photon_count: int = None,
                          photon_radius: float = None) -> dict:
