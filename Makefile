@@ -64,8 +64,9 @@ VALUBENCH := tools/bin/valu_issue
 MANUAL   := tests/c/bin/manual_scene
 LAYOUTCHECK := tests/c/bin/gpu_layout_check
 DISPATCHCHECK := tests/c/bin/dispatch_check
+FLATCHECK := tests/c/bin/flat_combine_check
 
-all: $(LIB) $(HOSTLIB) $(ORACLE) $(CLI) $(RCPCHECK) $(VALUBENCH) $(MANUAL) $(LAYOUTCHECK) $(DISPATCHCHECK)
+all: $(LIB) $(HOSTLIB) $(ORACLE) $(CLI) $(RCPCHECK) $(VALUBENCH) $(MANUAL) $(LAYOUTCHECK) $(DISPATCHCHECK) $(FLATCHECK)
 
 # C test: a scene description filled field by field (no XML loader), rendered through the C-ABI and
 # compared with the oracle (run by tests/test_gpu_parity.py)
@@ -85,6 +86,12 @@ $(LAYOUTCHECK): tests/c/gpu_layout_check.cpp $(HOSTLIB) $(PKG)/host/gpu_layout.h
 $(DISPATCHCHECK): tests/c/dispatch_check.cpp $(PKG)/csrc/nh_dispatch.h
 	@mkdir -p tests/c/bin
 	$(CXX) -std=c++17 -O2 -Wall -Wextra -I$(PKG)/csrc -o $@ $<
+
+# C++ test: the combine step of the flat two-leaf traversal (csrc/nh_flat_combine.h) on the CPU, no HIP (run by
+# tests/test_flat_combine_host.py)
+$(FLATCHECK): tests/c/flat_combine_check.cpp $(PKG)/csrc/nh_flat_combine.h
+	@mkdir -p tests/c/bin
+	$(CXX) -std=c++17 -O2 -Wall -Wextra $(FP_FLAGS) -I$(PKG)/csrc -o $@ $<
 
 # exhaustive check of the fast reciprocal the traversal kernels use (run by the GPU tests)
 $(RCPCHECK): tools/rcp_exhaustive.hip $(HIP_DEPS)

@@ -434,6 +434,11 @@ typedef struct nh_render_stats {
        kernels without collect_stats, the scene uploaded without NH_PAIR_KINDS=0 (read when the BVH is uploaded). 0: the
        reference arrangement, records paired in their own order. Cleared and set like primary_masks. */
     uint64_t pair_kinds;
+    /* 1 when the last render's fused bounce kernels took their queries without a tree walk (nh_flat_image: the scene's
+       tree is one leaf, or a root with two leaves, of at most 16 pair records): a wavefront render on the RR-ahead
+       bounce kernels with pair_kinds 1, the scene uploaded without NH_FLAT_TRACE=0 (read when the BVH is uploaded).
+       0: every query walks the tree. Cleared and set like primary_masks. */
+    uint64_t flat_trace;
 } nh_render_stats;
 
 typedef struct nh_scene nh_scene;
@@ -519,6 +524,17 @@ int32_t nh_primary_mask_pad(int32_t width, int32_t height);
  * two by two, then its spheres two by two; 0: the reference arrangement, position p = records (p, p + 1), both counts 0. */
 int nh_pair_layout(const float *records, int32_t n_records, const int32_t *leaves, int32_t n_leaves, int32_t by_kind,
                    int32_t *slots, int32_t *leaf_pairs);
+
+/* The flat image of a scene the fused bounce kernels traverse without a tree walk (host/gpu_layout.cpp flat_image; host
+ * only). records, leaves: as for nh_pair_layout, leaf 0 the root's left child and leaf 1 its right one (or the one leaf
+ * of the tree). boxes: 18 floats -- the root's box (min xyz, max xyz), the left child's, the right child's. allowed: the
+ * scene is staged in LDS with its pair records by kind. *n_f4 = 0: the scene is not flat (more than two leaves, more
+ * than 16 pair records, allowed 0 or NH_FLAT_TRACE=0); else the image's float4 count, and image (image_cap_f4 float4s
+ * of room) holds it: 6 header float4 (the three boxes, each leaf's triangle-pair and sphere-pair counts), then the pair
+ * records, 6 float4 each, the left leaf's first. *box_equal: bit 0 / bit 1 -- the left / right child's box is bit-equal
+ * to the root's. */
+int nh_flat_image(const float *records, int32_t n_records, const int32_t *leaves, int32_t n_leaves, const float *boxes,
+                  int32_t allowed, float *image, int32_t image_cap_f4, int32_t *n_f4, int32_t *box_equal);
 
 /* ImageBlock::toBitmap (src/utils/block.cpp:76-82): rgbw with border -> W*H*3 rgb */
 int nh_framebuffer_to_rgb(const float *rgbw, int32_t width, int32_t height, int32_t border, float *rgb);

@@ -210,6 +210,9 @@ struct nh_ctx {
     // without pair_kinds: small_image is that image).
     bool pair_kinds = false;
     float4 *small_image_ref = nullptr;
+    // the flat image of a scene whose tree is one leaf or a root with two leaves (host/gpu_layout.cpp flat_image, read
+    // by trace_flat of the non-counting RR-ahead bounce kernels; owned by bvh_bufs); null: not flat, or NH_FLAT_TRACE=0
+    const float4 *flat_image = nullptr;
     // Candidate masks of the camera rays' first closest hit (WfLaunch::pmask, host/primary_masks.cpp): built by
     // nh_render (ensure_primary_masks) from the uploaded camera, the primitive records (kept here when there are at
     // most 64) and the pixel list's blocks; every upload and every new pixel list frees them (drop_primary_masks), so

@@ -226,6 +226,9 @@ struct WfLaunch {
     // first_vertex of the non-STATS fused bounce kernels only.
     const unsigned long long *pmask;
     int pmask_nbx;
+    // The flat image of a scene whose tree is one leaf or a root with two leaves (nh_layout.h kFlatHeaderF4), or null:
+    // the non-STATS wf_bounce_rr kernels are launched in their FLAT instantiation with it (trace_flat).
+    const float4 *flat;
 };
 // persistent traversal grid: 16 workgroups of 128 lanes per CU (the 8 waves/SIMD its registers allow)
 constexpr int kPersistentBlocks = 256 * 16;

@@ -279,6 +279,11 @@ static int pool_start(nh_ctx *c, WfPool &p, const WfJob &job) {
     L.pmask_nbx = c->nbx;
     c->stats.primary_masks = masks ? 1 : 0;
     c->stats.pair_kinds = p.fused && c->pair_kinds && !j.stats ? 1 : 0;
+    // flat scenes (nh_upload.hip build_small_image): the non-counting RR-ahead bounce kernels take their queries
+    // without a tree walk (trace_flat). The Disney variant's kernels have no such copies.
+    const bool flat = p.rr && c->flat_image && c->pair_kinds && !j.stats && !c->disney;
+    L.flat = flat ? c->flat_image : nullptr;
+    c->stats.flat_trace = flat ? 1 : 0;
     c->stats.fused_bounce = p.fused ? 1 : 0;
     c->stats.node_bytes = p.wide ? 16 * nhd::kWideF4 * (c->wide_w / 4) : 64;
     c->stats.lds_scene = small && !p.persistent && c->depth <= 16 ? 1 : 0;  // the SMALL instantiations (DEPTH 16)
@@ -957,6 +962,7 @@ int nh_render(nh_ctx *c, const nh_render_req *q) {
     if (av_split && av_wide(c, q)) c->stats.node_bytes = 16 * nhd::kWideF4 * (c->wide_w / 4);
     c->stats.primary_masks = 0;
     c->stats.pair_kinds = 0;
+    c->stats.flat_trace = 0;
     c->stats.trace_fused = 0;
     c->stats.lds_scene = 0;
     c->stats.fused_bounce = 0;

@@ -24,6 +24,7 @@
 // reference accepts t <= maxt, so a later equal-t primitive overwrites).
 #pragma once
 #include "nh_device.h"
+#include "nh_flat_combine.h"
 
 namespace nhd {
 
@@ -290,7 +291,7 @@ struct Traversal {
 //       and k' their record indices; a = p0 (a sphere's centre and radius), e1 = p1 - p0, e2 = p2 - p0 (triangles
 //       only). A slot 0 without a partner is repeated in slot 1 (k' = k): the repeat yields the same candidate and
 //       loses the tie rule against itself, so it changes no answer.
-constexpr int kPairF4 = 6;
+// (kPairF4 = 6 float4 per pair: nh_layout.h, the host's flat image holds the same records)
 
 // primitive record bits (word 2 .w of the record): kPrimSphere, kPrimLeafEnd, kPrimMatShift, kPrimIsolated (nh_layout.h)
 NHD bool prim_is_tri(float4 c) { return (__float_as_int(c.w) & kPrimSphere) == 0; }
@@ -639,6 +640,114 @@ NHD bool trace(const Traversal &tv, const DScene &S, F3 o, F3 d, float mint, flo
     return ANY ? false : found;
 }
 
+// One leaf of a flat scene (trace_flat): its n_tri triangle pairs, then its n_sph sphere pairs, from the records at pp.
+// Trip counts and record addresses are the same for every lane, and the records are read-only for the kernel's length,
+// so the compiler can fetch them through the scalar cache into SGPRs: no LDS read, no per-lane address, no record
+// staged in VGPRs. The tests and the acceptance are leaf_test's by-kind loops'; best / found / maxt are this leaf's own.
+template <bool ANY, bool MASKED>
+NHD bool flat_leaf(const float4 *__restrict__ pp, int n_tri, int n_sph, F3 o, F3 d, float mint, float maxt, Hit &best,
+                   bool &found, unsigned long long cand) {
+    bool any = false;
+    for (int i = 0; i < n_tri; ++i, pp += kPairF4) {
+        const float4 q5 = pp[5];
+        const int k0 = __float_as_int(q5.z), k1 = __float_as_int(q5.w);
+        if constexpr (MASKED)
+            if (!(((cand >> (k0 & 63)) | (cand >> (k1 & 63))) & 1ull)) continue;
+        const float4 q0 = pp[0], q1 = pp[1], q2 = pp[2], q3 = pp[3], q4 = pp[4];
+        const P3 p0{f2{q0.x, q0.y}, f2{q0.z, q0.w}, f2{q1.x, q1.y}};
+        const P3 e1{f2{q2.x, q2.y}, f2{q2.z, q2.w}, f2{q3.x, q3.y}};
+        const P3 e2{f2{q3.z, q3.w}, f2{q4.x, q4.y}, f2{q4.z, q4.w}};
+        f2 pt, pu, pv;
+        bool ok0, ok1;
+        tri_test_pair_e(p0, e1, e2, o, d, mint, pt, pu, pv, ok0, ok1);
+        if (ANY) {
+            any = any || (ok0 && pt.x <= maxt) || (ok1 && pt.y <= maxt);
+            continue;
+        }
+        accept_hit(ok0 && pt.x <= maxt, pt.x, pu.x, pv.x, k0, maxt, best, found);
+        accept_hit(ok1 && pt.y <= maxt, pt.y, pu.y, pv.y, k1, maxt, best, found);
+    }
+    for (int i = 0; i < n_sph; ++i, pp += kPairF4) {
+        const float4 q5 = pp[5];
+        const int k0 = __float_as_int(q5.z), k1 = __float_as_int(q5.w);
+        if constexpr (MASKED)
+            if (!(((cand >> (k0 & 63)) | (cand >> (k1 & 63))) & 1ull)) continue;
+        const float4 q0 = pp[0], q1 = pp[1];
+        f2 tmin, tmax;
+        bool ok0, ok1;
+        sphere_test_pair(f2{q0.x, q0.y}, f2{q0.z, q0.w}, f2{q1.x, q1.y}, f2{q1.z, q1.w}, o, d, tmin, tmax, ok0, ok1);
+        if (!(ok0 | ok1)) continue;
+        float t0, t1;
+        const bool h0 = sphere_in_range(tmin.x, tmax.x, mint, maxt, t0) && ok0;
+        if (ANY) {
+            any = any || h0 || (sphere_in_range(tmin.y, tmax.y, mint, maxt, t1) && ok1);
+            continue;
+        }
+        accept_hit(h0, t0, 0.f, 0.f, k0, maxt, best, found);
+        const bool h1 = sphere_in_range(tmin.y, tmax.y, mint, maxt, t1) && ok1;
+        accept_hit(h1, t1, 0.f, 0.f, k1, maxt, best, found);
+    }
+    return any;
+}
+
+// trace() for a flat scene -- a tree of one leaf, or of a root whose two children are leaves -- from the scene's flat
+// image fl (nh_layout.h kFlatHeaderF4; host/gpu_layout.cpp flat_image): the same arithmetic (the adaptive epsilon, the
+// exits, the reciprocals, the box tests, the pair tests and their acceptance), without the walk: no stack, no node or
+// leaf-table fetch, the records read at addresses every lane shares. Root test, then both child boxes against the
+// entry maxt -- what trace() tests them with, nothing having been found yet; a child box bit-equal to the root's takes
+// the root's result (the same operations on the same values). Each leaf whose box the ray hits gives its own best
+// against the entry maxt (flat_leaf), and flat_combine (nh_flat_combine.h, where the argument is) makes of the two what
+// the walk in visit order returns. The second leaf's loop is skipped by the lanes for which the combine step cannot
+// take it (left first and the right box's entry past the left leaf's hit; any hit: the left leaf answered).
+template <bool ORDERED, bool ANY, bool RCP, bool MASKED = false>
+NHD bool trace_flat(const float4 *__restrict__ fl, const DScene &S, F3 o, F3 d, float mint, float maxt, Hit &best,
+                    unsigned long long cand = ~0ull) {
+    if (mint == kEps) mint = e_max(mint, mint * e_max(fabsf(o.x), e_max(fabsf(o.y), fabsf(o.z))));
+    best.k = -1;
+    best.t = INFINITY;
+    if (S.root_kind == 0 || maxt < mint) return false;
+    const F3 r = RCP ? f3(dir_rcp(d.x), dir_rcp(d.y), dir_rcp(d.z)) : f3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+    const bool fin = isfinite(r.x) & isfinite(r.y) & isfinite(r.z);
+    const float4 h0 = fl[0], h1 = fl[1], h2 = fl[2], h3 = fl[3], h4 = fl[4], h5 = fl[5];
+    const auto box = [&](float4 mn, float4 mx, float &near_t) {
+        return fin ? box_test_finite(mn.x, mn.y, mn.z, mx.x, mx.y, mx.z, o, r, mint, maxt, near_t)
+                   : box_test(mn.x, mn.y, mn.z, mx.x, mx.y, mx.z, o, d, r, mint, maxt, near_t);
+    };
+    float near_root;
+    if (!box(h0, h1, near_root)) return false;
+    const int eq = __float_as_int(h0.w);
+    const bool two = __float_as_int(h1.w) == 2;
+    bool hl = true, hr = false;
+    float nl = near_root, nr = near_root;
+    if (!(eq & kFlatLeftEq)) hl = box(h2, h3, nl);
+    if (two) {
+        hr = true;
+        if (!(eq & kFlatRightEq)) hr = box(h4, h5, nr);
+    }
+    const int cl = __float_as_int(h2.w), cr = __float_as_int(h4.w);
+    const float4 *pl = fl + kFlatHeaderF4, *pr = pl + kPairF4 * ((cl & 0xffff) + (cl >> 16));
+    Hit bl{INFINITY, 0.f, 0.f, -1}, br{INFINITY, 0.f, 0.f, -1};
+    bool fl_found = false, fr_found = false, any_l = false, any_r = false;
+    if (hl) any_l = flat_leaf<ANY, MASKED>(pl, cl & 0xffff, cl >> 16, o, d, mint, maxt, bl, fl_found, cand);
+    if constexpr (ANY) {
+        if (hr && !any_l) any_r = flat_leaf<ANY, MASKED>(pr, cr & 0xffff, cr >> 16, o, d, mint, maxt, br, fr_found, cand);
+        return flat_combine_any(hl, hr, any_l, any_r);
+    } else {
+        const bool left_first = hl && !(hr && ORDERED && nr < nl);
+        const float maxt_l = fl_found ? bl.t : maxt;
+        if (hr && !(left_first && !(nr <= maxt_l)))
+            flat_leaf<ANY, MASKED>(pr, cr & 0xffff, cr >> 16, o, d, mint, maxt, br, fr_found, cand);
+        FlatBest out;
+        flat_combine<ORDERED>(hl, hr, nl, nr, maxt, FlatBest{bl.t, bl.u, bl.v, bl.k, fl_found},
+                              FlatBest{br.t, br.u, br.v, br.k, fr_found}, out);
+        best.t = out.found ? out.t : INFINITY;
+        best.u = out.u;
+        best.v = out.v;
+        best.k = out.k;
+        return out.found;
+    }
+}
+
 // The closest hit of a path's next ray, which leaves the surface of primitive k_prev (-1: none). When k_prev is an
 // isolated sphere -- the host found its box, grown by 2m, apart from every other primitive's box -- and the ray
 // starts within m of that box and meets the sphere at t >= 2 mint, the traversal's answer is that sphere at that t,
@@ -679,6 +788,17 @@ NHD bool trace_next(const Traversal &tv, const DScene &S, int k_prev, F3 o, F3 d
         return true;
 #endif
     return trace<DEPTH, ORDERED, false, STATS, PAIRS, G, RCP>(tv, S, o, d, mint, maxt, best, stk, stride, st);
+}
+// trace_next for a flat scene: the same isolated-sphere answer in front, then trace_flat
+template <bool ORDERED, bool ISO = true, bool RCP = false>
+NHD bool trace_next_flat(const float4 *__restrict__ fl, const Traversal &tv, const DScene &S, int k_prev, F3 o, F3 d,
+                         float mint, float maxt, Hit &best) {
+#ifndef NH_AB_NO_ISO
+    TravStats none{0, 0, 0};
+    if (ISO && S.iso_spheres && S.root_kind != 0 && iso_sphere_hit<false, 1>(tv, k_prev, o, d, mint, maxt, best, none))
+        return true;
+#endif
+    return trace_flat<ORDERED, false, RCP>(fl, S, o, d, mint, maxt, best);
 }
 
 

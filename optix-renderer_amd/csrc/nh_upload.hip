@@ -421,6 +421,7 @@ int nh_upload_scene(nh_ctx *c, const nh_scene_desc *d) {
     c->h_area_cdf.assign(d->area_cdf, d->area_cdf + d->n_area_cdf);
     c->n_emit_faces = (int)ef_tri.size();
     c->small_image = c->small_image_ref = nullptr;  // (the BVH and its images went with bvh_bufs above)
+    c->flat_image = nullptr;
     c->pair_kinds = false;
     c->V.assign(d->V, d->V + 3 * nv);
     c->F.assign(d->F, d->F + 3 * (size_t)d->n_faces);
@@ -466,6 +467,7 @@ int nh_upload_scene(nh_ctx *c, const nh_scene_desc *d) {
 // arrangement), and then a second image in the reference arrangement for the counting kernels (nh_ctx::small_image_ref).
 static int build_small_image(nh_ctx *c, const nh::GpuBvh &g) {
     c->small_image = c->small_image_ref = nullptr;
+    c->flat_image = nullptr;
     c->pair_kinds = false;
     for (int &v : c->small_tab) v = 0;
     const size_t scene_bytes = 16 * (size_t)(c->n_node_f4 + c->n_prim_f4) + 8 * (size_t)c->n_leaves;
@@ -544,6 +546,39 @@ static int build_small_image(nh_ctx *c, const nh::GpuBvh &g) {
         }
         HIP_TRY(c, hipStreamSynchronize(c->stream));  // (pl and tab are locals)
         (pass == 0 ? c->small_image : c->small_image_ref) = img;
+    }
+    // The flat image (host/gpu_layout.cpp flat_image; NH_FLAT_TRACE=0: none): the tree is one leaf, or one inner node
+    // whose children are leaves 0 and 1, and the pair records by kind are few enough. The non-counting RR-ahead bounce
+    // kernels then take their queries from it without a tree walk (trace_flat).
+    const bool one_leaf = g.root_kind == 2 && c->n_leaves == 1;
+    bool two_leaves = g.root_kind == 1 && c->n_node_f4 == 4 && c->n_leaves == 2;
+    if (two_leaves) {
+        int refs[2];
+        std::memcpy(refs, &g.nodes[3].x, sizeof(refs));
+        two_leaves = refs[0] == ~0 && refs[1] == ~1;
+    }
+    if (c->pair_kinds && (one_leaf || two_leaves)) {
+        float boxes[18];
+        for (int i = 0; i < 3; ++i) {
+            boxes[i] = g.root_min[i];
+            boxes[3 + i] = g.root_max[i];
+        }
+        if (two_leaves) {
+            const nh::f4 n0 = g.nodes[0], n1 = g.nodes[1], n2 = g.nodes[2];
+            const float lr[12] = {n0.x, n0.y, n0.z, n0.w, n1.x, n1.y, n1.z, n1.w, n2.x, n2.y, n2.z, n2.w};
+            std::memcpy(boxes + 6, lr, sizeof(lr));
+        } else {
+            std::memcpy(boxes + 6, boxes, 6 * sizeof(float));
+            std::memcpy(boxes + 12, boxes, 6 * sizeof(float));
+        }
+        const nh::PairLayout pl = nh::pair_layout(g.leaves.data(), c->n_leaves, g.prims.data(), n, true);
+        const nh::FlatImage fi = nh::flat_image(boxes, g.leaves.data(), c->n_leaves, g.prims.data(), n, pl, nh::flat_trace_knob());
+        if (fi.flat) {
+            const nh::f4 *dev = nullptr;
+            if (int rc = upload(c, c->bvh_bufs, fi.data.data(), fi.data.size(), &dev)) return rc;
+            HIP_TRY(c, hipStreamSynchronize(c->stream));  // (fi is a local)
+            c->flat_image = reinterpret_cast<const float4 *>(dev);
+        }
     }
     return NH_OK;
 }

@@ -1226,10 +1226,11 @@ __device__ __forceinline__ void load_post_head(const DScene &S, const ST &T, con
 
 // the camera path of queue entry s at bounce 0, up to its first vertex's head
 // TRAIT: pinhole camera, trait head (shade_head)
-template <bool ORDERED, bool STATS, bool NMAP = true, bool TRAIT = false, class ST = DScene>
+// FLAT: the closest hit by trace_flat from the scene's flat image `flat` (no stack: stk is not read)
+template <bool ORDERED, bool STATS, bool NMAP = true, bool TRAIT = false, bool FLAT = false, class ST = DScene>
 __device__ __forceinline__ bool first_vertex(const DScene &S, const ST &T, const Traversal &tv, const WfLaunch &L, int s,
                                              PathV &v, Hit &h, Its &its, uint32_t *stk, int stride, TravStats &st_e,
-                                             unsigned long long &q_e) {
+                                             unsigned long long &q_e, const float4 *__restrict__ flat = nullptr) {
     float4 ro, rd;
     float jx, jy;
     // the ray's candidate records (leaf_test<.., MASKED>): its block's mask, or every record without a table. The
@@ -1258,9 +1259,12 @@ __device__ __forceinline__ bool first_vertex(const DScene &S, const ST &T, const
     v.pid = s;
     const bool live = rd.w >= ro.w;
     q_e += live ? 1 : 0;
-    const bool found =
-        live && trace<16, ORDERED, false, STATS, true, 1, TRAIT, MASKED>(tv, S, v.org, v.d, ro.w, rd.w, h, stk, stride,
-                                                                        st_e, cand);
+    bool found;
+    if constexpr (FLAT)
+        found = live && trace_flat<ORDERED, false, TRAIT, MASKED>(flat, S, v.org, v.d, ro.w, rd.w, h, cand);
+    else
+        found = live && trace<16, ORDERED, false, STATS, true, 1, TRAIT, MASKED>(tv, S, v.org, v.d, ro.w, rd.w, h, stk,
+                                                                                stride, st_e, cand);
     if (!shade_head<NMAP, TRAIT>(S, T, tv, v, h, found, 0.f, its)) {
         write_radiance(L, v);
         return false;
@@ -1284,11 +1288,15 @@ struct TailClocks {
 // TRAIT: the diffuse area-light body and head; the stream increment stays in its registers over the step instead of
 // being re-derived from the path id (path_of), and the traversals take the guarded fast reciprocal (trace<.., RCP>)
 // LEAN: the caller drops its afterwards (shade_head)
+// FLAT (G = 1, no STATS): both queries by trace_flat from the scene's flat image `flat`, behind trace_next's
+// isolated-sphere answer (no stack: stk is not read)
 template <bool ORDERED, bool STATS, bool CLK = false, int G = 1, bool FULL = true, bool NMAP = FULL, bool TRAIT = false,
-          bool LEAN = false, class ST = DScene>
+          bool LEAN = false, bool FLAT = false, class ST = DScene>
 __device__ __forceinline__ bool rr_step(const DScene &S, const ST &T, const Traversal &tv, const WfLaunch &L, PathV &v, Its &its,
                                         Hit &h, uint32_t *stk, int stride, TravStats &st_e, TravStats &st_s,
-                                        unsigned long long &q_e, unsigned long long &q_s, TailClocks *clk = nullptr) {
+                                        unsigned long long &q_e, unsigned long long &q_s, TailClocks *clk = nullptr,
+                                        const float4 *__restrict__ flat = nullptr) {
+    static_assert(!FLAT || (G == 1 && !STATS), "the flat traversal carries one ray per lane and counts nothing");
     const bool lead = G == 1 || (threadIdx.x & (G - 1)) == 0;
     PState o;
     bool nee = false;
@@ -1306,7 +1314,10 @@ __device__ __forceinline__ bool rr_step(const DScene &S, const ST &T, const Trav
     if (nee) {  // the light sample's any-hit query, its outcome applied as the next shade_path would
         Hit hs;
         if (lead) ++q_s;
-        if (!trace<16, ORDERED, true, STATS, true, G, TRAIT>(tv, S, xyz(so), xyz(sd), so.w, sd.w, hs, stk, stride, st_s)) {
+        bool occluded;
+        if constexpr (FLAT) occluded = trace_flat<ORDERED, true, TRAIT>(flat, S, xyz(so), xyz(sd), so.w, sd.w, hs);
+        else occluded = trace<16, ORDERED, true, STATS, true, G, TRAIT>(tv, S, xyz(so), xyz(sd), so.w, sd.w, hs, stk, stride, st_s);
+        if (!occluded) {
             o.li.x = o.li.x + o.pe.x;
             o.li.y = o.li.y + o.pe.y;
             o.li.z = o.li.z + o.pe.z;
@@ -1325,8 +1336,12 @@ __device__ __forceinline__ bool rr_step(const DScene &S, const ST &T, const Trav
     }
     const bool live = o.rd.w >= o.ro.w;
     if (lead) q_e += live ? 1 : 0;
-    const bool found = live && trace_next<16, ORDERED, STATS, true, G, FULL, TRAIT>(tv, S, h.k, xyz(o.ro), xyz(o.rd),
-                                                                             o.ro.w, o.rd.w, h, stk, stride, st_e);
+    bool found;
+    if constexpr (FLAT)
+        found = live && trace_next_flat<ORDERED, FULL, TRAIT>(flat, tv, S, h.k, xyz(o.ro), xyz(o.rd), o.ro.w, o.rd.w, h);
+    else
+        found = live && trace_next<16, ORDERED, STATS, true, G, FULL, TRAIT>(tv, S, h.k, xyz(o.ro), xyz(o.rd), o.ro.w,
+                                                                            o.rd.w, h, stk, stride, st_e);
     if constexpr (CLK) {
         t1 = clock64();
         if (lead) cs[2] += t1 - t0;
@@ -1368,11 +1383,13 @@ __device__ __forceinline__ bool rr_step(const DScene &S, const ST &T, const Trav
 // BOUNCE: -1 bounce 0 or a later one, by L.first; 0 / 1 the kernel runs only bounce 0 / only later bounces, so the other
 // entry's code (camera sample and first closest hit, or the state unpacking) is not compiled in. pre: the path's
 // stored words when the kernel loaded them ahead of its staging barrier (BOUNCE = 1), else null.
-template <bool ORDERED, bool STATS, bool FULL, bool NMAP = FULL, bool TRAIT = false, int BOUNCE = -1, class ST = DScene>
+template <bool ORDERED, bool STATS, bool FULL, bool NMAP = FULL, bool TRAIT = false, int BOUNCE = -1, bool FLAT = false,
+          class ST = DScene>
 __device__ __forceinline__ bool bounce_path(const DScene &S, const ST &T, const Traversal &tv, const WfLaunch &L, const QView &qv,
                                             int q, uint32_t *my_stk, PathV &v, Hit &h, TravStats &st_e,
                                             TravStats &st_s, unsigned long long &q_e, unsigned long long &q_s,
-                                            TailClocks &clk, unsigned long long &c_load, const RawState *pre = nullptr) {
+                                            TailClocks &clk, unsigned long long &c_load, const RawState *pre = nullptr,
+                                            const float4 *__restrict__ flat = nullptr) {
     Its its;
     bool alive = true;
     unsigned long long t_ph = 0;
@@ -1380,7 +1397,8 @@ __device__ __forceinline__ bool bounce_path(const DScene &S, const ST &T, const 
     const bool first = BOUNCE < 0 ? L.first != 0 : BOUNCE == 0;
     if (first) {
         const int s = queue_slot(qv.pre, L.seg_cap, q);
-        alive = first_vertex<ORDERED, STATS, NMAP, TRAIT>(S, T, tv, L, s, v, h, its, my_stk, NH_BOUNCE_TB, st_e, q_e);
+        alive = first_vertex<ORDERED, STATS, NMAP, TRAIT, FLAT>(S, T, tv, L, s, v, h, its, my_stk, NH_BOUNCE_TB, st_e, q_e,
+                                                                flat);
     } else if (BOUNCE == 1) {
         unpack_post_head<NMAP>(S, T, tv, L, *pre, v, h, its);
     } else {
@@ -1388,16 +1406,20 @@ __device__ __forceinline__ bool bounce_path(const DScene &S, const ST &T, const 
     }
     if constexpr (STATS) c_load += clock64() - t_ph;
     // its is dropped here: the next launch recomputes it from the stored hit (unpack_post_head)
-    return alive && rr_step<ORDERED, STATS, STATS, 1, FULL, NMAP, TRAIT, true>(S, T, tv, L, v, its, h, my_stk,
-                                                                         NH_BOUNCE_TB, st_e, st_s, q_e, q_s, &clk);
+    return alive && rr_step<ORDERED, STATS, STATS, 1, FULL, NMAP, TRAIT, true, FLAT>(S, T, tv, L, v, its, h, my_stk, NH_BOUNCE_TB,
+                                                                               st_e, st_s, q_e, q_s, &clk, flat);
 }
 
 // TRAIT, BOUNCE: the diffuse area-light instantiations (launch_wf_bounce_trait), one for bounce 0 and one for the later
 // bounces; the later-bounce kernel issues its path's state loads before the staging barrier and uses them after it
-template <bool ORDERED, bool STATS, bool SORT, bool FULL = true, bool NMAP = FULL, bool TRAIT = false, int BOUNCE = -1>
+// FLAT (flat scenes, never with STATS): the three queries by trace_flat from the flat image `flat` (L.flat, passed as
+// an argument of its own so that it is a restrict pointer whose loads can go through the scalar cache): no stacks
+template <bool ORDERED, bool STATS, bool SORT, bool FULL = true, bool NMAP = FULL, bool TRAIT = false, int BOUNCE = -1,
+          bool FLAT = false>
 __global__ __launch_bounds__(NH_BOUNCE_TB, NH_DZ_WAVES(true, NH_BOUNCE_WAVES)) void wf_bounce_rr(const DScene *__restrict__ Sp, Traversal tv_g,
-                                                                     WfLaunch L) {
-    __shared__ uint32_t stk[16 * NH_BOUNCE_TB];
+                                                                     WfLaunch L, const float4 *__restrict__ flat) {
+    static_assert(!(FLAT && STATS), "the counting kernels walk the tree");
+    __shared__ uint32_t stk[FLAT ? 1 : 16 * NH_BOUNCE_TB];
     __shared__ unsigned s_n[kMatClasses], s_off[kMatClasses], s_base;
     extern __shared__ float4 lds_scene[];
     const QView qv = queue_view(L.cnt_in);
@@ -1411,7 +1433,7 @@ __global__ __launch_bounds__(NH_BOUNCE_TB, NH_DZ_WAVES(true, NH_BOUNCE_WAVES)) v
         if (q < qv.n) pre = load_raw_state(L.st.buf[L.in_q], queue_slot(qv.pre, L.seg_cap, q));
     const Traversal tv = stage_small_scene<true>(tv_g, L, lds_scene);
     const int shard = blockIdx.x & (kQueueShards - 1);
-    uint32_t *my_stk = stk + threadIdx.x;
+    uint32_t *my_stk = FLAT ? stk : stk + threadIdx.x;
     TravStats st_e{0, 0, 0}, st_s{0, 0, 0};
     unsigned long long q_e = 0, q_s = 0;
     bool cont = false;
@@ -1424,8 +1446,8 @@ __global__ __launch_bounds__(NH_BOUNCE_TB, NH_DZ_WAVES(true, NH_BOUNCE_WAVES)) v
     unsigned long long c_load = 0, c_store = 0, t_ph = 0;
     if (q < qv.n) {
         const auto &T = scene_tables<TRAIT && NH_TRAIT_TABLES>(S, L, lds_scene);
-        cont = bounce_path<ORDERED, STATS, FULL, NMAP, TRAIT, BOUNCE>(S, T, tv, L, qv, q, my_stk, v, h, st_e, st_s, q_e, q_s,
-                                                                      clk, c_load, BOUNCE == 1 ? &pre : nullptr);
+        cont = bounce_path<ORDERED, STATS, FULL, NMAP, TRAIT, BOUNCE, FLAT>(S, T, tv, L, qv, q, my_stk, v, h, st_e, st_s, q_e,
+                                                                            q_s, clk, c_load, BOUNCE == 1 ? &pre : nullptr, flat);
         if (cont) cls = prim_material(tv.prims[3 * h.k + 2]);  // a live path's ray has hit something
         if constexpr (STATS) t_ph = clock64();
     }
@@ -1816,14 +1838,28 @@ void launch_wf_bounce_rr(const DScene *S, const Traversal &tv, const WfLaunch &L
     int blocks = std::max(1, (bound + NH_BOUNCE_TB - 1) / NH_BOUNCE_TB);
     blocks = (blocks + kQueueShards - 1) / kQueueShards * kQueueShards;
     const size_t lds = 16 * (size_t)rr_lds_f4(L);
-    const auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(blocks), dim3(NH_BOUNCE_TB), lds, st, S, tv, L); };
+    const auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(NH_BOUNCE_TB), lds, st, S, tv, L, L.flat);
+    };
+    // flat scenes (L.flat): the FLAT copies, which exist without STATS only (and not in the Disney variant)
+#ifndef NH_DISNEY
+    const bool flat = L.flat != nullptr && !stats;
+#else
+    const bool flat = false;
+#endif
     // the two trimmed bodies are built for near-first traversal only
     if (ordered && lean) {  // no discrete BSDF, no texture: wf_bounce_rr<.., FULL = false>
-        nh_dispatch([&](auto T, auto SO) { launch(wf_bounce_rr<true, T, SO, false>); }, stats, sort);
+        nh_dispatch([&](auto T, auto SO, auto FL) {
+            if constexpr (!(T && FL) && !(kDisney && FL)) launch(wf_bounce_rr<true, T, SO, false, false, false, -1, FL>);
+        }, stats, sort, flat);
     } else if (ordered && !nmap) {  // the full body without normal maps: wf_bounce_rr<.., FULL = true, NMAP = false>
-        nh_dispatch([&](auto T, auto SO) { launch(wf_bounce_rr<true, T, SO, true, false>); }, stats, sort);
+        nh_dispatch([&](auto T, auto SO, auto FL) {
+            if constexpr (!(T && FL) && !(kDisney && FL)) launch(wf_bounce_rr<true, T, SO, true, false, false, -1, FL>);
+        }, stats, sort, flat);
     } else {
-        nh_dispatch([&](auto O, auto T, auto SO) { launch(wf_bounce_rr<O, T, SO>); }, ordered, stats, sort);
+        nh_dispatch([&](auto O, auto T, auto SO, auto FL) {
+            if constexpr (!(T && FL) && !(kDisney && FL)) launch(wf_bounce_rr<O, T, SO, true, true, false, -1, FL>);
+        }, ordered, stats, sort, flat);
     }
 }
 
@@ -1874,11 +1910,12 @@ void launch_wf_bounce_trait(const DScene *S, const Traversal &tv, const WfLaunch
     int blocks = std::max(1, (bound + NH_BOUNCE_TB - 1) / NH_BOUNCE_TB);
     blocks = (blocks + kQueueShards - 1) / kQueueShards * kQueueShards;
     const size_t lds = 16 * (size_t)rr_lds_f4(L);
-    nh_dispatch([&](auto FIRST, auto T) {
+    nh_dispatch([&](auto FIRST, auto T, auto FL) {
         constexpr int BOUNCE = NH_TRAIT_SPLIT ? (FIRST ? 0 : 1) : -1;  // bounce 0 / the later ones, or one copy for both
-        hipLaunchKernelGGL((wf_bounce_rr<true, T, false, false, false, true, BOUNCE>), dim3(blocks), dim3(NH_BOUNCE_TB),
-                           lds, st, S, tv, L);
-    }, L.first != 0, stats);
+        if constexpr (!(T && FL))  // (flat scenes, L.flat: the FLAT copies, without STATS only)
+            hipLaunchKernelGGL((wf_bounce_rr<true, T, false, false, false, true, BOUNCE, FL>), dim3(blocks),
+                               dim3(NH_BOUNCE_TB), lds, st, S, tv, L, L.flat);
+    }, L.first != 0, stats, L.flat != nullptr && !stats);
 }
 
 void launch_wf_tail_trait(const DScene *S, const Traversal &tv, const WfLaunch &L, bool stats, int bound, int coop,

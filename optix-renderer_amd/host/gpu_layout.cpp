@@ -607,9 +607,95 @@ PairLayout pair_layout(const i2 *leaves, int n_leaves, const f4 *prims, int n_re
     return out;
 }
 
+bool flat_trace_knob() {
+    const char *e = std::getenv("NH_FLAT_TRACE");
+    return !(e && e[0] == '0');
+}
+
+FlatImage flat_image(const float boxes[18], const i2 *leaves, int n_leaves, const f4 *prims, int n_records,
+                     const PairLayout &pl, bool allowed) {
+    FlatImage out;
+    if (!allowed || n_leaves < 1 || n_leaves > 2 || n_records < 1 || (int)pl.leaves.size() != n_leaves) return out;
+    int n_pairs = 0;
+    for (int l = 0; l < n_leaves; ++l) {
+        const int2 p = pl.leaves[(size_t)l];
+        if (p.y == 0 && leaves[l].y > 0) return out;  // (not an arrangement by kind)
+        n_pairs += (p.y & 0xffff) + (p.y >> 16);
+    }
+    if (n_pairs < 1 || n_pairs > nhd::kFlatMaxPairs) return out;
+    const auto same_bits = [](const float *a, const float *b) { return std::memcmp(a, b, 6 * sizeof(float)) == 0; };
+    const auto as_float = [](int v) {
+        float f;
+        std::memcpy(&f, &v, 4);
+        return f;
+    };
+    const float *root = boxes, *lb = n_leaves == 2 ? boxes + 6 : boxes, *rb = n_leaves == 2 ? boxes + 12 : boxes;
+    out.box_equal = n_leaves == 1 ? nhd::kFlatLeftEq
+                                  : (same_bits(lb, root) ? nhd::kFlatLeftEq : 0) | (same_bits(rb, root) ? nhd::kFlatRightEq : 0);
+    out.data.reserve((size_t)nhd::kFlatHeaderF4 + (size_t)nhd::kPairF4 * n_pairs);
+    out.data.push_back(make_float4(root[0], root[1], root[2], as_float(out.box_equal)));
+    out.data.push_back(make_float4(root[3], root[4], root[5], as_float(n_leaves)));
+    out.data.push_back(make_float4(lb[0], lb[1], lb[2], as_float(pl.leaves[0].y)));
+    out.data.push_back(make_float4(lb[3], lb[4], lb[5], 0.f));
+    out.data.push_back(make_float4(rb[0], rb[1], rb[2], as_float(n_leaves == 2 ? pl.leaves[1].y : 0)));
+    out.data.push_back(make_float4(rb[3], rb[4], rb[5], 0.f));
+    for (int l = 0; l < n_leaves; ++l) {
+        const int2 p = pl.leaves[(size_t)l];
+        for (int i = 0, n = (p.y & 0xffff) + (p.y >> 16); i < n; ++i) {
+            const int2 s = pl.slots[(size_t)(p.x + i)];
+            const int k = s.x, k1 = s.y < 0 ? k : s.y;
+            if (k < 0 || k >= n_records || k1 >= n_records) return FlatImage{};  // (a layout of other leaves)
+            // the pair record of build_pairs_frames (csrc/nh_wavefront.hip), by the same float subtractions
+            const float4 a = prims[3 * (size_t)k], b = prims[3 * (size_t)k + 1], c = prims[3 * (size_t)k + 2];
+            const float4 a1 = prims[3 * (size_t)k1], b1 = prims[3 * (size_t)k1 + 1], c1 = prims[3 * (size_t)k1 + 2];
+            out.data.push_back(make_float4(a.x, a1.x, a.y, a1.y));
+            out.data.push_back(make_float4(a.z, a1.z, a.w, a1.w));
+            out.data.push_back(make_float4(b.x - a.x, b1.x - a1.x, b.y - a.y, b1.y - a1.y));
+            out.data.push_back(make_float4(b.z - a.z, b1.z - a1.z, c.x - a.x, c1.x - a1.x));
+            out.data.push_back(make_float4(c.y - a.y, c1.y - a1.y, c.z - a.z, c1.z - a1.z));
+            out.data.push_back(make_float4(c.w, c1.w, as_float(k), as_float(k1)));
+        }
+    }
+    out.flat = true;
+    return out;
+}
+
 }  // namespace nh
 
 extern "C" {
+
+int nh_flat_image(const float *records, int32_t n_records, const int32_t *leaves, int32_t n_leaves, const float *boxes,
+                  int32_t allowed, float *image, int32_t image_cap_f4, int32_t *n_f4, int32_t *box_equal) {
+    bool ok = n_records >= 0 && n_leaves >= 0 && (n_records == 0 || records) && (n_leaves == 0 || leaves) && boxes &&
+              n_f4 && box_equal && image_cap_f4 >= 0 && (image_cap_f4 == 0 || image);
+    std::vector<char> used((size_t)std::max(n_records, 0), 0);  // (as nh_pair_layout)
+    for (int l = 0; ok && l < n_leaves; ++l) {
+        const int64_t s = leaves[2 * l], n = leaves[2 * l + 1];
+        ok = s >= 0 && n >= 0 && n < 65535 && s + n <= n_records;
+        for (int64_t k = s; ok && k < s + n; ++k) {
+            ok = !used[(size_t)k];
+            used[(size_t)k] = 1;
+        }
+    }
+    if (!ok) {
+        nh::set_host_error("nh_flat_image: invalid argument");
+        return NH_ERR_INVALID;
+    }
+    const nh::i2 *lv = reinterpret_cast<const nh::i2 *>(leaves);
+    const nh::f4 *rec = reinterpret_cast<const nh::f4 *>(records);
+    const nh::PairLayout pl = nh::pair_layout(lv, n_leaves, rec, n_records, true);
+    const nh::FlatImage fi = nh::flat_image(boxes, lv, n_leaves, rec, n_records, pl, allowed != 0 && nh::flat_trace_knob());
+    *n_f4 = fi.flat ? (int32_t)fi.data.size() : 0;
+    *box_equal = fi.box_equal;
+    if (fi.flat) {
+        if ((size_t)image_cap_f4 < fi.data.size()) {
+            nh::set_host_error("nh_flat_image: image buffer too small");
+            return NH_ERR_INVALID;
+        }
+        std::memcpy(image, fi.data.data(), fi.data.size() * sizeof(nh::f4));
+    }
+    return NH_OK;
+}
 
 int nh_pair_layout(const float *records, int32_t n_records, const int32_t *leaves, int32_t n_leaves, int32_t by_kind,
                    int32_t *slots, int32_t *leaf_pairs) {

@@ -82,4 +82,24 @@ struct PairLayout {
 };
 PairLayout pair_layout(const i2 *leaves, int n_leaves, const f4 *prims, int n_records, bool by_kind);
 
+// The flat image of a scene the fused bounce kernels traverse without a tree walk (csrc/nh_traverse.h trace_flat; the
+// format: csrc/nh_layout.h kFlatHeaderF4). A scene is flat when `allowed` (the caller's part: the scene is staged
+// small, its pair records are arranged by kind, and flat_trace_knob()), its tree is one leaf (n_leaves 1) or a root
+// whose two children are both leaves (n_leaves 2: leaf 0 the left child, leaf 1 the right one), and pl -- the
+// arrangement by kind of those leaves -- has at most kFlatMaxPairs pair positions in use.
+//   boxes: 18 floats -- the root's box (min xyz, max xyz), the left child's, the right child's (one leaf: the last two
+//          are not read)
+//   data:  the image (empty when not flat); its pair records hold what the device computes for the LDS image's: p0, the
+//          edges p1 - p0 and p2 - p0 by the same IEEE subtractions, the flag words and the record indices
+//   box_equal: kFlatLeftEq / kFlatRightEq bits -- the child's six bounds have the bit patterns of the root's
+struct FlatImage {
+    bool flat = false;
+    int box_equal = 0;
+    std::vector<f4> data;
+};
+FlatImage flat_image(const float boxes[18], const i2 *leaves, int n_leaves, const f4 *prims, int n_records,
+                     const PairLayout &pl, bool allowed);
+// NH_FLAT_TRACE=0 (read at every call; the BVH upload calls it once) turns flat traversal off
+bool flat_trace_knob();
+
 }  // namespace nh

@@ -205,7 +205,7 @@ class nh_render_stats(C.Structure):
                                   "tail_coop_bounces", "bounce_cycles_load", "bounce_cycles_body",
                                   "bounce_cycles_shadow", "bounce_cycles_closest", "bounce_cycles_head",
                                   "bounce_cycles_store", "bounce_bounces", "bounce_traits", "primary_masks",
-                                  "pair_kinds")]
+                                  "pair_kinds", "flat_trace")]
 
 
 def _sig(name, res, *args):
@@ -238,6 +238,7 @@ _sig("nh_primary_masks", _i32, C.POINTER(nh_camera), _fp, _i32, C.POINTER(_i32),
      C.POINTER(_i32))
 _sig("nh_primary_mask_pad", _i32, _i32, _i32)
 _sig("nh_pair_layout", _i32, _fp, _i32, C.POINTER(_i32), _i32, _i32, C.POINTER(_i32), C.POINTER(_i32))
+_sig("nh_flat_image", _i32, _fp, _i32, C.POINTER(_i32), _i32, _fp, _i32, _fp, _i32, C.POINTER(_i32), C.POINTER(_i32))
 _sig("nh_framebuffer_to_rgb", _i32, _fp, _i32, _i32, _i32, _fp)
 _sig("nh_write_pfm", _i32, C.c_char_p, _fp, _i32, _i32)
 _sig("nh_image_load_png", _i32, C.c_char_p, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(_i32), C.POINTER(_i32))
@@ -954,6 +955,22 @@ def pair_layout(records: np.ndarray, leaves, by_kind: bool = True):
     _host_check(_lib.nh_pair_layout(_fptr(rec), len(rec), lv.ctypes.data_as(ip), len(lv), 1 if by_kind else 0,
                                     slots.ctypes.data_as(ip), lp.ctypes.data_as(ip)), "pair_layout")
     return slots, lp
+
+
+def flat_image(records: np.ndarray, leaves, boxes, allowed: bool = True):
+    """nh_flat_image: the flat image of a tree of one leaf or of a root with two leaves -- `leaves` its (start, count)
+    rows, `boxes` the root's, left child's and right child's boxes (18 floats: min xyz, max xyz each). Returns (image,
+    box_equal): image (n, 4) float32 -- 6 header rows, then 6 rows per pair record -- or None when the scene is not flat;
+    box_equal bit 0 / 1: the left / right child's box is bit-equal to the root's."""
+    rec = np.ascontiguousarray(records, dtype=np.float32).reshape(-1, 12)
+    lv = np.ascontiguousarray(leaves, dtype=np.int32).reshape(-1, 2)
+    bx = np.ascontiguousarray(boxes, dtype=np.float32).ravel()
+    assert bx.size == 18
+    cap = 6 + 6 * 16
+    img, n, eq = np.zeros((cap, 4), np.float32), _i32(0), _i32(0)
+    _host_check(_lib.nh_flat_image(_fptr(rec), len(rec), lv.ctypes.data_as(C.POINTER(_i32)), len(lv), _fptr(bx),
+                                   1 if allowed else 0, _fptr(img), cap, C.byref(n), C.byref(eq)), "flat_image")
+    return (img[:n.value].copy() if n.value else None), int(eq.value)
 
 
 def reduce_framebuffers(ctxs, root: int = 0):
