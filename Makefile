@@ -22,7 +22,7 @@ HIP_FLAGS  := -std=c++17 -O3 -fPIC --offload-arch=$(ARCH) $(FP_FLAGS) \
 
 HOST_SRC := $(PKG)/host/xml_lite.cpp $(PKG)/host/scene_loader.cpp $(PKG)/host/bvh_build.cpp $(PKG)/host/image_io.cpp \
             $(PKG)/host/png_decode.cpp $(PKG)/host/hdr_decode.cpp $(PKG)/host/gpu_layout.cpp $(PKG)/host/ttest.cpp \
-            $(PKG)/host/photon_host.cpp $(PKG)/host/primary_masks.cpp
+            $(PKG)/host/photon_host.cpp $(PKG)/host/primary_masks.cpp $(PKG)/host/shadow_masks.cpp
 HIP_SRC  := $(PKG)/csrc/nh_kernels.hip $(PKG)/csrc/nh_denoise.hip $(PKG)/csrc/nh_splat.hip $(PKG)/csrc/nh_api.hip \
             $(PKG)/csrc/nh_upload.hip $(PKG)/csrc/nh_pipeline.hip $(PKG)/csrc/nh_adaptive_api.hip $(PKG)/csrc/nh_query_api.hip \
             $(PKG)/csrc/nh_photon_api.hip $(PKG)/csrc/nh_av.hip

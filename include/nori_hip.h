@@ -439,6 +439,12 @@ typedef struct nh_render_stats {
        bounce kernels with pair_kinds 1, the scene uploaded without NH_FLAT_TRACE=0 (read when the BVH is uploaded).
        0: every query walks the tree. Cleared and set like primary_masks. */
     uint64_t flat_trace;
+    /* which candidate masks the light samples' any-hit queries of the last render's RR-ahead bounce kernels ran with
+       (nh_shadow_masks): 0 none, 2 the per-block words at bounce 0 (each holds the emitter-side word's zeros). Level 1
+       -- the emitter-side word alone, at every bounce -- was measured and is not built: the field never reads 1, and
+       NH_SHADOW_MASKS=1 gives 0 like NH_SHADOW_MASKS=0. 2 needs what primary_masks needs, that table, and a scene
+       whose emitters are all area lights on meshes without vertex normals. Cleared and set like primary_masks. */
+    uint64_t shadow_masks;
 } nh_render_stats;
 
 typedef struct nh_scene nh_scene;
@@ -516,6 +522,20 @@ void nh_bvh_free(nh_bvh *bvh);
 int nh_primary_masks(const nh_camera *camera, const float *records, int32_t n_records, const int32_t *blocks,
                      int32_t n_blocks, uint64_t *masks, int32_t *built);
 int32_t nh_primary_mask_pad(int32_t width, int32_t height);
+
+/* Candidate masks of the light sample's any-hit query (host/shadow_masks.cpp; host only). records, blocks: as for
+ * nh_primary_masks. emit_faces: n_emit_faces emitter faces of 9 floats (three vertices) -- every face of every emitter
+ * when all of them are area lights on meshes without vertex normals, else n_emit_faces = 0. *emitter_mask bit k clear:
+ * no shadow ray (from an emitter face, leaving on its front side, no longer than the scene) can be accepted by record
+ * k; all ones when nothing can be left out. *built = 1 and masks[i] bit k clear when no shadow ray ending at a first
+ * hit of block blocks[i]'s camera rays can be accepted by record k (each word holds *emitter_mask's zeros as well);
+ * *built = 0 (masks untouched) when nh_primary_masks builds no table. */
+/* The emitter faces nh_shadow_masks takes, as nh_render forms them: *n_faces faces of 9 floats, 0 unless every emitter
+ * of the scene is an area light on a mesh without vertex normals. faces has room for cap_faces of them. */
+int nh_shadow_emitter_faces(const nh_scene_desc *scene, float *faces, int32_t cap_faces, int32_t *n_faces);
+int nh_shadow_masks(const nh_camera *camera, const float *records, int32_t n_records, const float *emit_faces,
+                    int32_t n_emit_faces, const int32_t *blocks, int32_t n_blocks, uint64_t *emitter_mask,
+                    uint64_t *masks, int32_t *built);
 
 /* Which primitive records share a pair record of a small scene's LDS image (host/gpu_layout.cpp pair_layout; host
  * only). records: as for nh_primary_masks; leaves: n_leaves (start, count) ranges of records, disjoint. slots: 2 ints per

@@ -82,6 +82,7 @@ void nh_destroy(nh_ctx *c) {
     (void)hipFree(c->rec);
     c->px.release();
     (void)hipFree(c->pmask);
+    (void)hipFree(c->smask);
     (void)hipFree(c->block_rank);
     (void)hipFree(c->staging);
     free_all(c->av_bufs);

@@ -221,6 +221,11 @@ struct nh_ctx {
     std::vector<float> h_prims;  // 12 floats per record, as uploaded; empty: more than 64 records
     unsigned long long *pmask = nullptr;
     bool pmask_known = false;
+    // Candidate masks of bounce 0's light samples (WfLaunch::smask; host/shadow_masks.cpp), built and freed with pmask.
+    // h_emit_tris: the emitter faces' vertices, 9 floats each, when every emitter is an area light on a mesh without
+    // vertex normals (else empty: no table). smask is null without a pmask table.
+    std::vector<float> h_emit_tris;
+    unsigned long long *smask = nullptr;
     float *fb = nullptr;
     size_t fb_floats = 0;
     float *rec = nullptr;  // (r, g, b) per sample
@@ -245,7 +250,9 @@ struct nh_ctx {
 // Frees the context's candidate-mask table. The caller has drained the pipeline (no chunk in flight reads it).
 inline void drop_primary_masks(nh_ctx *c) {
     (void)hipFree(c->pmask);
+    (void)hipFree(c->smask);
     c->pmask = nullptr;
+    c->smask = nullptr;
     c->pmask_known = false;
 }
 

@@ -226,6 +226,9 @@ struct WfLaunch {
     // first_vertex of the non-STATS fused bounce kernels only.
     const unsigned long long *pmask;
     int pmask_nbx;
+    // Candidate masks of the light sample's any-hit query at bounce 0 (host/shadow_masks.cpp), indexed as pmask; null:
+    // every record is tested. Read by rr_step of the non-STATS wf_bounce_rr kernels that run bounce 0.
+    const unsigned long long *smask;
     // The flat image of a scene whose tree is one leaf or a root with two leaves (nh_layout.h kFlatHeaderF4), or null:
     // the non-STATS wf_bounce_rr kernels are launched in their FLAT instantiation with it (trace_flat).
     const float4 *flat;

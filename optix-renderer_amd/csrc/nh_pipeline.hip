@@ -278,6 +278,12 @@ static int pool_start(nh_ctx *c, WfPool &p, const WfJob &job) {
     L.pmask = masks ? c->pmask : nullptr;
     L.pmask_nbx = c->nbx;
     c->stats.primary_masks = masks ? 1 : 0;
+    // bounce 0's light samples' candidate masks (rr_step of the same kernels): level 2, the per-block words.
+    // NH_SHADOW_MASKS=0 or 1: none (level 1, the emitter-side word alone at every bounce, was measured and removed).
+    const char *sm = std::getenv("NH_SHADOW_MASKS");
+    const bool shadow = p.rr && c->smask && !j.stats && !(sm && (sm[0] == '0' || sm[0] == '1'));
+    L.smask = shadow ? c->smask : nullptr;
+    c->stats.shadow_masks = shadow ? 2 : 0;
     c->stats.pair_kinds = p.fused && c->pair_kinds && !j.stats ? 1 : 0;
     // flat scenes (nh_upload.hip build_small_image): the non-counting RR-ahead bounce kernels take their queries
     // without a tree walk (trace_flat). The Disney variant's kernels have no such copies.
@@ -818,6 +824,21 @@ static int ensure_primary_masks(nh_ctx *c) {
         HIP_TRY(c, e);
     }
     c->pmask = d;
+    // the light samples' candidate masks, for the same records and blocks (absent with the table above)
+    const int n_faces = (int)(c->h_emit_tris.size() / 9);
+    const nh::f4 *recs = reinterpret_cast<const nh::f4 *>(c->h_prims.data());
+    const int n_recs = (int)(c->h_prims.size() / 12);
+    if (n_faces == 0 ||
+        !nh::shadow_block_masks(c->camera, recs, n_recs, c->h_emit_tris.data(), n_faces, blocks.data(), (int)blocks.size(), m))
+        return NH_OK;
+    for (size_t i = 0; i < blocks.size(); ++i) grid[(size_t)blocks[i]] = m[i];
+    HIP_TRY(c, hipMalloc(&d, std::max<size_t>(grid.size(), 1) * sizeof(unsigned long long)));
+    const hipError_t e2 = hipMemcpy(d, grid.data(), grid.size() * sizeof(unsigned long long), hipMemcpyHostToDevice);
+    if (e2 != hipSuccess) {
+        (void)hipFree(d);
+        HIP_TRY(c, e2);
+    }
+    c->smask = d;
     return NH_OK;
 }
 
@@ -961,6 +982,7 @@ int nh_render(nh_ctx *c, const nh_render_req *q) {
     c->stats.node_bytes = 64;  // binary tree unless a wavefront pool picks the 4-wide one
     if (av_split && av_wide(c, q)) c->stats.node_bytes = 16 * nhd::kWideF4 * (c->wide_w / 4);
     c->stats.primary_masks = 0;
+    c->stats.shadow_masks = 0;
     c->stats.pair_kinds = 0;
     c->stats.flat_trace = 0;
     c->stats.trace_fused = 0;

@@ -420,6 +420,10 @@ int nh_upload_scene(nh_ctx *c, const nh_scene_desc *d) {
     c->h_emitters = de;
     c->h_area_cdf.assign(d->area_cdf, d->area_cdf + d->n_area_cdf);
     c->n_emit_faces = (int)ef_tri.size();
+    // the emitter faces the shadow masks reason from (host/shadow_masks.cpp): kept only when every light sample
+    // starts on one of them
+    c->h_emit_tris = nh::shadow_emitter_faces(*d);
+    if (c->h_emit_tris.size() != 9 * ef_tri.size()) c->h_emit_tris.clear();  // (NH_EMIT_FACES=0: no record to start from)
     c->small_image = c->small_image_ref = nullptr;  // (the BVH and its images went with bvh_bufs above)
     c->flat_image = nullptr;
     c->pair_kinds = false;

@@ -1227,10 +1227,13 @@ __device__ __forceinline__ void load_post_head(const DScene &S, const ST &T, con
 // the camera path of queue entry s at bounce 0, up to its first vertex's head
 // TRAIT: pinhole camera, trait head (shade_head)
 // FLAT: the closest hit by trace_flat from the scene's flat image `flat` (no stack: stk is not read)
+// sblk: where given, receives the block of the path's pixel (camera_sample's blk): rr_step looks the light sample's
+// candidate records up under it
 template <bool ORDERED, bool STATS, bool NMAP = true, bool TRAIT = false, bool FLAT = false, class ST = DScene>
 __device__ __forceinline__ bool first_vertex(const DScene &S, const ST &T, const Traversal &tv, const WfLaunch &L, int s,
                                              PathV &v, Hit &h, Its &its, uint32_t *stk, int stride, TravStats &st_e,
-                                             unsigned long long &q_e, const float4 *__restrict__ flat = nullptr) {
+                                             unsigned long long &q_e, const float4 *__restrict__ flat = nullptr,
+                                             int *sblk = nullptr) {
     float4 ro, rd;
     float jx, jy;
     // the ray's candidate records (leaf_test<.., MASKED>): its block's mask, or every record without a table. The
@@ -1241,10 +1244,11 @@ __device__ __forceinline__ bool first_vertex(const DScene &S, const ST &T, const
     constexpr bool MASKED = false;
 #endif
     unsigned long long cand = ~0ull;
-    if constexpr (MASKED) {
+    if constexpr (!STATS) {
         int blk;
         camera_sample<!TRAIT>(S, L, s, v.rng, ro, rd, jx, jy, &blk);
-        if (L.pmask) cand = L.pmask[blk];
+        if (MASKED && L.pmask) cand = L.pmask[blk];
+        if (sblk) *sblk = blk;
     } else {
         camera_sample<!TRAIT>(S, L, s, v.rng, ro, rd, jx, jy);
     }
@@ -1290,13 +1294,17 @@ struct TailClocks {
 // LEAN: the caller drops its afterwards (shade_head)
 // FLAT (G = 1, no STATS): both queries by trace_flat from the scene's flat image `flat`, behind trace_next's
 // isolated-sphere answer (no stack: stk is not read)
+// SMASK (G = 1, no STATS; the bounce kernels that run bounce 0): at bounce 0 (s_blk: each thread's block index, in LDS)
+// with a per-block table (L.smask, host/shadow_masks.cpp) the light sample's any-hit query tests only the candidate
+// records of the wave's blocks. Leaving out a record that cannot accept the ray does not change an OR.
 template <bool ORDERED, bool STATS, bool CLK = false, int G = 1, bool FULL = true, bool NMAP = FULL, bool TRAIT = false,
-          bool LEAN = false, bool FLAT = false, class ST = DScene>
+          bool LEAN = false, bool FLAT = false, bool SMASK = false, class ST = DScene>
 __device__ __forceinline__ bool rr_step(const DScene &S, const ST &T, const Traversal &tv, const WfLaunch &L, PathV &v, Its &its,
                                         Hit &h, uint32_t *stk, int stride, TravStats &st_e, TravStats &st_s,
                                         unsigned long long &q_e, unsigned long long &q_s, TailClocks *clk = nullptr,
-                                        const float4 *__restrict__ flat = nullptr) {
+                                        const float4 *__restrict__ flat = nullptr, const int *s_blk = nullptr) {
     static_assert(!FLAT || (G == 1 && !STATS), "the flat traversal carries one ray per lane and counts nothing");
+    static_assert(!SMASK || (G == 1 && !STATS), "the counting and cooperative queries test every record");
     const bool lead = G == 1 || (threadIdx.x & (G - 1)) == 0;
     PState o;
     bool nee = false;
@@ -1315,8 +1323,27 @@ __device__ __forceinline__ bool rr_step(const DScene &S, const ST &T, const Trav
         Hit hs;
         if (lead) ++q_s;
         bool occluded;
-        if constexpr (FLAT) occluded = trace_flat<ORDERED, true, TRAIT>(flat, S, xyz(so), xyz(sd), so.w, sd.w, hs);
-        else occluded = trace<16, ORDERED, true, STATS, true, G, TRAIT>(tv, S, xyz(so), xyz(sd), so.w, sd.w, hs, stk, stride, st_s);
+        [[maybe_unused]] unsigned long long scand = ~0ull;
+        if constexpr (SMASK) {
+            // bounce 0: the union of the entries of the blocks this wave's light samples belong to (mostly one block)
+            // -- a superset of each lane's candidates, the same for every lane, so the word stays in scalar registers
+            // and a pair no lane needs is skipped by a scalar branch
+            if (s_blk && L.smask) {
+                const int sblk = s_blk[threadIdx.x];
+                unsigned long long acc = 0;
+                for (unsigned long long rem = __ballot(1); rem;) {
+                    const int b = __builtin_amdgcn_readlane(sblk, __ffsll((long long)rem) - 1);
+                    acc |= L.smask[b];
+                    rem &= ~__ballot(sblk == b);
+                }
+                scand = acc;
+            }
+        }
+        if constexpr (FLAT)
+            occluded = trace_flat<ORDERED, true, TRAIT, SMASK>(flat, S, xyz(so), xyz(sd), so.w, sd.w, hs, scand);
+        else
+            occluded = trace<16, ORDERED, true, STATS, true, G, TRAIT, SMASK>(tv, S, xyz(so), xyz(sd), so.w, sd.w, hs, stk,
+                                                                             stride, st_s, scand);
         if (!occluded) {
             o.li.x = o.li.x + o.pe.x;
             o.li.y = o.li.y + o.pe.y;
@@ -1395,10 +1422,16 @@ __device__ __forceinline__ bool bounce_path(const DScene &S, const ST &T, const 
     unsigned long long t_ph = 0;
     if constexpr (STATS) t_ph = clock64();
     const bool first = BOUNCE < 0 ? L.first != 0 : BOUNCE == 0;
+    // bounce 0: the path's block, for the light sample's candidate records (rr_step). It waits in LDS over the first
+    // hit, the head and the body: in a register (or as the 64-bit word itself) it takes the bounce-0 trait FLAT kernel
+    // from 78 to 82-84 VGPRs, past the 80 of its sixth wave per SIMD.
+    __shared__ int s_blk[NH_BOUNCE_TB];
+    bool sblk = false;
     if (first) {
         const int s = queue_slot(qv.pre, L.seg_cap, q);
         alive = first_vertex<ORDERED, STATS, NMAP, TRAIT, FLAT>(S, T, tv, L, s, v, h, its, my_stk, NH_BOUNCE_TB, st_e, q_e,
-                                                                flat);
+                                                                flat, &s_blk[threadIdx.x]);
+        sblk = true;
     } else if (BOUNCE == 1) {
         unpack_post_head<NMAP>(S, T, tv, L, *pre, v, h, its);
     } else {
@@ -1406,8 +1439,12 @@ __device__ __forceinline__ bool bounce_path(const DScene &S, const ST &T, const 
     }
     if constexpr (STATS) c_load += clock64() - t_ph;
     // its is dropped here: the next launch recomputes it from the stored hit (unpack_post_head)
-    return alive && rr_step<ORDERED, STATS, STATS, 1, FULL, NMAP, TRAIT, true, FLAT>(S, T, tv, L, v, its, h, my_stk, NH_BOUNCE_TB,
-                                                                               st_e, st_s, q_e, q_s, &clk, flat);
+    // (the later-bounce trait kernels have no masked query: the emitter-side word alone did not pay for its scalar
+    // tests)
+    constexpr bool SMASK = !STATS && BOUNCE != 1;
+    return alive && rr_step<ORDERED, STATS, STATS, 1, FULL, NMAP, TRAIT, true, FLAT, SMASK>(S, T, tv, L, v, its, h, my_stk,
+                                                                                       NH_BOUNCE_TB, st_e, st_s, q_e, q_s,
+                                                                                       &clk, flat, sblk ? s_blk : nullptr);
 }
 
 // TRAIT, BOUNCE: the diffuse area-light instantiations (launch_wf_bounce_trait), one for bounce 0 and one for the later

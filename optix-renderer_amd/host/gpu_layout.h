@@ -67,6 +67,24 @@ bool primary_masks(const nh_camera &cam, const f4 *prims, int n_records, const i
                    std::vector<uint64_t> &masks);
 // the pad in pixels a block's rectangle is grown by: at least 2, a 256th of the larger image side
 int primary_mask_pad(int width, int height);
+// in_front[k]: every point of record k passes the masks' in-front-of-camera condition (else the record is a candidate
+// of every block). False when primary_masks would build no table.
+bool primary_mask_in_front(const nh_camera &cam, const f4 *prims, int n_records, std::vector<char> &in_front);
+
+// Candidate masks of the light sample's any-hit query (shadow_masks.cpp). emit_faces: the vertices of every emitter
+// face, 9 floats each -- n_faces > 0 only when every emitter of the scene is an area light on a mesh without vertex
+// normals (the caller's part), else 0: nothing is left out.
+// The emitter-side word: bit k clear when no shadow ray of any bounce can be accepted by record k (all ones with more
+// than 64 records).
+uint64_t shadow_emitter_mask(const f4 *prims, int n_records, const float *emit_faces, int n_faces);
+// The emit_faces of a scene: every emitting face's vertices when every emitter is an area light on a mesh without vertex
+// normals; empty otherwise (a point, spot, directional or envmap light, a sphere light, a mesh light with normals).
+std::vector<float> shadow_emitter_faces(const nh_scene_desc &d);
+// The per-block words of bounce 0 (indexing and absence as primary_masks): masks[i] bit k clear when no shadow ray
+// that ends at a first hit of block blocks[i]'s camera rays can be accepted by record k. Each holds the emitter-side
+// word's zeros too.
+bool shadow_block_masks(const nh_camera &cam, const f4 *prims, int n_records, const float *emit_faces, int n_faces,
+                        const int32_t *blocks, int n_blocks, std::vector<uint64_t> &masks);
 
 // Which records share a pair record of a small scene's LDS image (csrc/nh_traverse.h leaf_test<.., PAIRS>). There are
 // as many pair positions as records; a leaf's pairs start at the position of its first record.

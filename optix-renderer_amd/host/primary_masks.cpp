@@ -91,9 +91,17 @@ struct Projector {
 
 int primary_mask_pad(int width, int height) { return std::max(2, (std::max(width, height) + 255) / 256); }
 
-bool primary_masks(const nh_camera &cam, const f4 *prims, int n_records, const int32_t *blocks, int n_blocks,
-                   std::vector<uint64_t> &masks) {
-    masks.clear();
+namespace {
+
+// the raster bounding box of a record; everywhere: a candidate for every block (one of its points fails
+// Projector::raster's in-front-of-camera condition)
+struct Box {
+    bool everywhere;
+    double x0, y0, x1, y1;
+};
+
+// every record's raster box; false when the feature is absent (more than 64 records, a lens, a singular transform)
+bool record_boxes(const nh_camera &cam, const f4 *prims, int n_records, std::vector<Box> &box) {
     if (n_records < 0 || n_records > 64 || cam.lens_radius > 1e-4f || cam.width <= 0 || cam.height <= 0) return false;
     Projector pr;
     if (!invert4(cam.camera_to_world, pr.w2c)) return false;
@@ -104,12 +112,7 @@ bool primary_masks(const nh_camera &cam, const f4 *prims, int n_records, const i
     const float *cw = cam.camera_to_world;
     const V3 org{(double)cw[3] / cw[15], (double)cw[7] / cw[15], (double)cw[11] / cw[15]};
 
-    // the raster bounding box of every record; everywhere: a candidate for every block
-    struct Box {
-        bool everywhere;
-        double x0, y0, x1, y1;
-    };
-    std::vector<Box> box((size_t)n_records);
+    box.assign((size_t)n_records, Box{});
     for (int k = 0; k < n_records; ++k) {
         const f4 a = prims[3 * k], b = prims[3 * k + 1], c = prims[3 * k + 2];
         int bits;
@@ -148,6 +151,24 @@ bool primary_masks(const nh_camera &cam, const f4 *prims, int n_records, const i
         }
         box[(size_t)k] = bx;
     }
+    return true;
+}
+
+}  // namespace
+
+bool primary_mask_in_front(const nh_camera &cam, const f4 *prims, int n_records, std::vector<char> &in_front) {
+    std::vector<Box> box;
+    in_front.clear();
+    if (!record_boxes(cam, prims, n_records, box)) return false;
+    for (const Box &b : box) in_front.push_back(b.everywhere ? 0 : 1);
+    return true;
+}
+
+bool primary_masks(const nh_camera &cam, const f4 *prims, int n_records, const int32_t *blocks, int n_blocks,
+                   std::vector<uint64_t> &masks) {
+    masks.clear();
+    std::vector<Box> box;
+    if (!record_boxes(cam, prims, n_records, box)) return false;
 
     const double pad = primary_mask_pad(cam.width, cam.height);
     const int nbx = (cam.width + 31) / 32, nby = (cam.height + 31) / 32;

@@ -205,7 +205,7 @@ class nh_render_stats(C.Structure):
                                   "tail_coop_bounces", "bounce_cycles_load", "bounce_cycles_body",
                                   "bounce_cycles_shadow", "bounce_cycles_closest", "bounce_cycles_head",
                                   "bounce_cycles_store", "bounce_bounces", "bounce_traits", "primary_masks",
-                                  "pair_kinds", "flat_trace")]
+                                  "pair_kinds", "flat_trace", "shadow_masks")]
 
 
 def _sig(name, res, *args):
@@ -237,6 +237,9 @@ _sig("nh_bvh_free", None, _vp)
 _sig("nh_primary_masks", _i32, C.POINTER(nh_camera), _fp, _i32, C.POINTER(_i32), _i32, C.POINTER(C.c_uint64),
      C.POINTER(_i32))
 _sig("nh_primary_mask_pad", _i32, _i32, _i32)
+_sig("nh_shadow_emitter_faces", _i32, C.POINTER(nh_scene_desc), _fp, _i32, C.POINTER(_i32))
+_sig("nh_shadow_masks", _i32, C.POINTER(nh_camera), _fp, _i32, _fp, _i32, C.POINTER(_i32), _i32, C.POINTER(C.c_uint64),
+     C.POINTER(C.c_uint64), C.POINTER(_i32))
 _sig("nh_pair_layout", _i32, _fp, _i32, C.POINTER(_i32), _i32, _i32, C.POINTER(_i32), C.POINTER(_i32))
 _sig("nh_flat_image", _i32, _fp, _i32, C.POINTER(_i32), _i32, _fp, _i32, _fp, _i32, C.POINTER(_i32), C.POINTER(_i32))
 _sig("nh_framebuffer_to_rgb", _i32, _fp, _i32, _i32, _i32, _fp)
@@ -941,6 +944,31 @@ def primary_masks(camera: nh_camera, records: np.ndarray, blocks):
                                       len(blk), out.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(built)),
                 "primary_masks")
     return out if built.value else None
+
+
+def shadow_emitter_faces(desc: nh_scene_desc):
+    """nh_shadow_emitter_faces: (n, 9) float32, the vertices of every emitter face of the scene when all its emitters
+    are area lights on meshes without vertex normals; else empty."""
+    out, n = np.zeros((max(int(desc.n_faces), 1), 9), np.float32), _i32(0)
+    _host_check(_lib.nh_shadow_emitter_faces(C.byref(desc), _fptr(out), len(out), C.byref(n)), "shadow_emitter_faces")
+    return out[:n.value].copy()
+
+
+def shadow_masks(camera: nh_camera, records: np.ndarray, emit_faces, blocks):
+    """nh_shadow_masks: (emitter_word, masks) for the light samples' any-hit queries. emit_faces: (n, 9) float32, the
+    vertices of every emitter face when every emitter is an area light on a mesh without vertex normals, else None or
+    empty. emitter_word: an int whose clear bit k says no shadow ray can be accepted by record k (all ones: nothing is
+    left out). masks: per block of `blocks` a uint64 with the same meaning for the shadow rays of that block's first
+    hits, or None when the per-block table is absent (as primary_masks)."""
+    rec = np.ascontiguousarray(records, dtype=np.float32).reshape(-1, 12)
+    blk = np.ascontiguousarray(blocks, dtype=np.int32).ravel()
+    ef = np.zeros((0, 9), np.float32) if emit_faces is None else np.ascontiguousarray(emit_faces, np.float32).reshape(-1, 9)
+    out = np.zeros(len(blk), np.uint64)
+    word, built = C.c_uint64(0), _i32(0)
+    _host_check(_lib.nh_shadow_masks(C.byref(camera), _fptr(rec), len(rec), _fptr(ef), len(ef),
+                                     blk.ctypes.data_as(C.POINTER(_i32)), len(blk), C.byref(word),
+                                     out.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(built)), "shadow_masks")
+    return int(word.value), (out if built.value else None)
 
 
 def pair_layout(records: np.ndarray, leaves, by_kind: bool = True):
