@@ -445,6 +445,12 @@ typedef struct nh_render_stats {
        NH_SHADOW_MASKS=1 gives 0 like NH_SHADOW_MASKS=0. 2 needs what primary_masks needs, that table, and a scene
        whose emitters are all area lights on meshes without vertex normals. Cleared and set like primary_masks. */
     uint64_t shadow_masks;
+    /* how many primitive records the light samples' any-hit queries of the last render's flat bounce kernels could
+       test: the records the scene-wide any-hit word keeps (nh_shadow_any_word), read from the flat image's any-hit
+       section (nh_flat_image_any). 0: no section -- the scene is not flat, nothing can be left out, NH_ANY_LIST=0 (read
+       when the BVH is uploaded) -- and those queries test the closest-hit pair records. Cleared and set like
+       primary_masks. */
+    uint64_t any_list;
 } nh_render_stats;
 
 typedef struct nh_scene nh_scene;
@@ -536,6 +542,13 @@ int nh_shadow_emitter_faces(const nh_scene_desc *scene, float *faces, int32_t ca
 int nh_shadow_masks(const nh_camera *camera, const float *records, int32_t n_records, const float *emit_faces,
                     int32_t n_emit_faces, const int32_t *blocks, int32_t n_blocks, uint64_t *emitter_mask,
                     uint64_t *masks, int32_t *built);
+/* The scene-wide any-hit word (host/shadow_masks.cpp; host only): *word bit k clear when no shadow ray of any bounce
+ * can be accepted by record k -- *emitter_mask's zeros, and the supporting walls: triangle records with every emitter
+ * vertex well in front of their plane and every hit point of the scene on that same side, which a shadow ray, ending
+ * 1e-4 short of its far end, does not reach. The camera gives the longest ray that can hit a sphere. All ones when
+ * nothing can be left out (as *emitter_mask). */
+int nh_shadow_any_word(const nh_camera *camera, const float *records, int32_t n_records, const float *emit_faces,
+                       int32_t n_emit_faces, uint64_t *word);
 
 /* Which primitive records share a pair record of a small scene's LDS image (host/gpu_layout.cpp pair_layout; host
  * only). records: as for nh_primary_masks; leaves: n_leaves (start, count) ranges of records, disjoint. slots: 2 ints per
@@ -555,6 +568,15 @@ int nh_pair_layout(const float *records, int32_t n_records, const int32_t *leave
  * to the root's. */
 int nh_flat_image(const float *records, int32_t n_records, const int32_t *leaves, int32_t n_leaves, const float *boxes,
                   int32_t allowed, float *image, int32_t image_cap_f4, int32_t *n_f4, int32_t *box_equal);
+/* nh_flat_image with the scene-wide any-hit word (nh_shadow_any_word; all ones: nh_flat_image's image). Unless every
+ * record's bit is set (or NH_ANY_LIST=0) the image carries an any-hit section, which the light samples' any-hit
+ * queries read instead of the pair records: bit 2 of header word [0].w is set, [3].w and [5].w hold the left and the
+ * right leaf's any-hit counts (triangle pairs | sphere pairs << 16), and at float4 6 + 6 * 16 -- zeros in between --
+ * follow pair records of each leaf's kept records, paired among themselves by nh_pair_layout's by-kind rules, the
+ * left leaf's first. The image then has up to 6 + 6 * 32 float4. *box_equal is nh_flat_image's. */
+int nh_flat_image_any(const float *records, int32_t n_records, const int32_t *leaves, int32_t n_leaves,
+                      const float *boxes, int32_t allowed, uint64_t any_word, float *image, int32_t image_cap_f4,
+                      int32_t *n_f4, int32_t *box_equal);
 
 /* ImageBlock::toBitmap (src/utils/block.cpp:76-82): rgbw with border -> W*H*3 rgb */
 int nh_framebuffer_to_rgb(const float *rgbw, int32_t width, int32_t height, int32_t border, float *rgb);

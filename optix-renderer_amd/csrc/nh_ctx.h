@@ -213,6 +213,9 @@ struct nh_ctx {
     // the flat image of a scene whose tree is one leaf or a root with two leaves (host/gpu_layout.cpp flat_image, read
     // by trace_flat of the non-counting RR-ahead bounce kernels; owned by bvh_bufs); null: not flat, or NH_FLAT_TRACE=0
     const float4 *flat_image = nullptr;
+    // records in the flat image's any-hit section (host/shadow_masks.cpp shadow_any_word: what the light samples'
+    // any-hit queries test instead of every record); 0: the image has no such section (NH_ANY_LIST=0, nothing left out)
+    int flat_any_records = 0;
     // Candidate masks of the camera rays' first closest hit (WfLaunch::pmask, host/primary_masks.cpp): built by
     // nh_render (ensure_primary_masks) from the uploaded camera, the primitive records (kept here when there are at
     // most 64) and the pixel list's blocks; every upload and every new pixel list frees them (drop_primary_masks), so

@@ -290,6 +290,7 @@ static int pool_start(nh_ctx *c, WfPool &p, const WfJob &job) {
     const bool flat = p.rr && c->flat_image && c->pair_kinds && !j.stats && !c->disney;
     L.flat = flat ? c->flat_image : nullptr;
     c->stats.flat_trace = flat ? 1 : 0;
+    c->stats.any_list = flat ? (uint64_t)c->flat_any_records : 0;  // (the image's any-hit section, read by trace_flat)
     c->stats.fused_bounce = p.fused ? 1 : 0;
     c->stats.node_bytes = p.wide ? 16 * nhd::kWideF4 * (c->wide_w / 4) : 64;
     c->stats.lds_scene = small && !p.persistent && c->depth <= 16 ? 1 : 0;  // the SMALL instantiations (DEPTH 16)
@@ -985,6 +986,7 @@ int nh_render(nh_ctx *c, const nh_render_req *q) {
     c->stats.shadow_masks = 0;
     c->stats.pair_kinds = 0;
     c->stats.flat_trace = 0;
+    c->stats.any_list = 0;
     c->stats.trace_fused = 0;
     c->stats.lds_scene = 0;
     c->stats.fused_bounce = 0;

@@ -717,15 +717,27 @@ NHD bool trace_flat(const float4 *__restrict__ fl, const DScene &S, F3 o, F3 d, 
     if (!box(h0, h1, near_root)) return false;
     const int eq = __float_as_int(h0.w);
     const bool two = __float_as_int(h1.w) == 2;
-    bool hl = true, hr = false;
+    // An any-hit query reads the image's any-hit section when there is one (kFlatAnyList): pair records of the records
+    // that can occlude a light sample at all (host/shadow_masks.cpp shadow_any_word), each leaf's own, so the answer
+    // -- an OR over the tests of the records in the leaves whose boxes are hit -- is the same. Counts and base are the
+    // same for every lane (scalar loads); a leaf without such records needs no box test.
+    int cl = __float_as_int(h2.w), cr = __float_as_int(h4.w);
+    const float4 *pl = fl + kFlatHeaderF4;
+    if constexpr (ANY) {
+        if (eq & kFlatAnyList) {
+            cl = __float_as_int(h3.w);
+            cr = __float_as_int(h5.w);
+            pl = fl + kFlatAnyOff;
+        }
+    }
+    bool hl = !ANY || cl != 0, hr = false;
     float nl = near_root, nr = near_root;
-    if (!(eq & kFlatLeftEq)) hl = box(h2, h3, nl);
-    if (two) {
+    if (hl && !(eq & kFlatLeftEq)) hl = box(h2, h3, nl);
+    if (two && (!ANY || cr != 0)) {
         hr = true;
         if (!(eq & kFlatRightEq)) hr = box(h4, h5, nr);
     }
-    const int cl = __float_as_int(h2.w), cr = __float_as_int(h4.w);
-    const float4 *pl = fl + kFlatHeaderF4, *pr = pl + kPairF4 * ((cl & 0xffff) + (cl >> 16));
+    const float4 *pr = pl + kPairF4 * ((cl & 0xffff) + (cl >> 16));
     Hit bl{INFINITY, 0.f, 0.f, -1}, br{INFINITY, 0.f, 0.f, -1};
     bool fl_found = false, fr_found = false, any_l = false, any_r = false;
     if (hl) any_l = flat_leaf<ANY, MASKED>(pl, cl & 0xffff, cl >> 16, o, d, mint, maxt, bl, fl_found, cand);

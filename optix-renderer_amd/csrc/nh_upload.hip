@@ -426,6 +426,7 @@ int nh_upload_scene(nh_ctx *c, const nh_scene_desc *d) {
     if (c->h_emit_tris.size() != 9 * ef_tri.size()) c->h_emit_tris.clear();  // (NH_EMIT_FACES=0: no record to start from)
     c->small_image = c->small_image_ref = nullptr;  // (the BVH and its images went with bvh_bufs above)
     c->flat_image = nullptr;
+    c->flat_any_records = 0;
     c->pair_kinds = false;
     c->V.assign(d->V, d->V + 3 * nv);
     c->F.assign(d->F, d->F + 3 * (size_t)d->n_faces);
@@ -472,6 +473,7 @@ int nh_upload_scene(nh_ctx *c, const nh_scene_desc *d) {
 static int build_small_image(nh_ctx *c, const nh::GpuBvh &g) {
     c->small_image = c->small_image_ref = nullptr;
     c->flat_image = nullptr;
+    c->flat_any_records = 0;
     c->pair_kinds = false;
     for (int &v : c->small_tab) v = 0;
     const size_t scene_bytes = 16 * (size_t)(c->n_node_f4 + c->n_prim_f4) + 8 * (size_t)c->n_leaves;
@@ -576,7 +578,15 @@ static int build_small_image(nh_ctx *c, const nh::GpuBvh &g) {
             std::memcpy(boxes + 12, boxes, 6 * sizeof(float));
         }
         const nh::PairLayout pl = nh::pair_layout(g.leaves.data(), c->n_leaves, g.prims.data(), n, true);
-        const nh::FlatImage fi = nh::flat_image(boxes, g.leaves.data(), c->n_leaves, g.prims.data(), n, pl, nh::flat_trace_knob());
+        // the scene-wide any-hit word (host/shadow_masks.cpp; NH_ANY_LIST=0: all ones): the records it keeps get pair
+        // records of their own in the image, which the light samples' any-hit queries read
+        uint64_t any_word = ~(uint64_t)0;
+        if (nh::any_list_knob() && n <= 64 && !c->h_emit_tris.empty())
+            any_word = nh::shadow_any_word(c->camera, g.prims.data(), n, c->h_emit_tris.data(), (int)(c->h_emit_tris.size() / 9));
+        const nh::FlatImage fi = nh::flat_image(boxes, g.leaves.data(), c->n_leaves, g.prims.data(), n, pl, nh::flat_trace_knob(),
+                                                any_word);
+        if (fi.flat && fi.any_list)
+            for (int k = 0; k < n; ++k) c->flat_any_records += (int)((any_word >> k) & 1);
         if (fi.flat) {
             const nh::f4 *dev = nullptr;
             if (int rc = upload(c, c->bvh_bufs, fi.data.data(), fi.data.size(), &dev)) return rc;

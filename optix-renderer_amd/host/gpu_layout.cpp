@@ -613,7 +613,7 @@ bool flat_trace_knob() {
 }
 
 FlatImage flat_image(const float boxes[18], const i2 *leaves, int n_leaves, const f4 *prims, int n_records,
-                     const PairLayout &pl, bool allowed) {
+                     const PairLayout &pl, bool allowed, uint64_t any_word) {
     FlatImage out;
     if (!allowed || n_leaves < 1 || n_leaves > 2 || n_records < 1 || (int)pl.leaves.size() != n_leaves) return out;
     int n_pairs = 0;
@@ -630,31 +630,63 @@ FlatImage flat_image(const float boxes[18], const i2 *leaves, int n_leaves, cons
         return f;
     };
     const float *root = boxes, *lb = n_leaves == 2 ? boxes + 6 : boxes, *rb = n_leaves == 2 ? boxes + 12 : boxes;
+    // The any-hit section: each leaf's kept records (any_word) paired again by pair_layout's rules -- a leaf of their
+    // own ranges would split the records, so the kept ones are listed and paired here the same way: triangles two by
+    // two in record order, then spheres, a lone record repeated. None when nothing is left out.
+    const uint64_t in_use = n_records < 64 ? ~(~(uint64_t)0 << n_records) : ~(uint64_t)0;
+    const bool any_list = n_records <= 64 && (any_word & in_use) != in_use;
+    std::vector<int2> any_slots[2];
+    int any_counts[2] = {0, 0};
+    if (any_list)
+        for (int l = 0; l < n_leaves; ++l) {
+            std::vector<int> kind[2];
+            for (int k = leaves[l].x; k < leaves[l].x + leaves[l].y; ++k) {
+                if (k < 0 || k >= n_records) return out;
+                if (!((any_word >> k) & 1)) continue;
+                int bits;
+                std::memcpy(&bits, &prims[3 * (size_t)k + 2].w, 4);
+                kind[bits & nhd::kPrimSphere ? 1 : 0].push_back(k);
+            }
+            for (const std::vector<int> &v : kind)
+                for (size_t i = 0; i < v.size(); i += 2)
+                    any_slots[l].push_back(make_int2(v[i], i + 1 < v.size() ? v[i + 1] : -1));
+            any_counts[l] = ((int)kind[0].size() + 1) / 2 | (((int)kind[1].size() + 1) / 2) << 16;
+        }
+    out.any_list = any_list;
     out.box_equal = n_leaves == 1 ? nhd::kFlatLeftEq
                                   : (same_bits(lb, root) ? nhd::kFlatLeftEq : 0) | (same_bits(rb, root) ? nhd::kFlatRightEq : 0);
-    out.data.reserve((size_t)nhd::kFlatHeaderF4 + (size_t)nhd::kPairF4 * n_pairs);
-    out.data.push_back(make_float4(root[0], root[1], root[2], as_float(out.box_equal)));
+    out.data.reserve((size_t)nhd::kFlatHeaderF4 + (size_t)nhd::kPairF4 * (any_list ? 2 * nhd::kFlatMaxPairs : n_pairs));
+    out.data.push_back(make_float4(root[0], root[1], root[2], as_float(out.box_equal | (any_list ? nhd::kFlatAnyList : 0))));
     out.data.push_back(make_float4(root[3], root[4], root[5], as_float(n_leaves)));
     out.data.push_back(make_float4(lb[0], lb[1], lb[2], as_float(pl.leaves[0].y)));
-    out.data.push_back(make_float4(lb[3], lb[4], lb[5], 0.f));
+    out.data.push_back(make_float4(lb[3], lb[4], lb[5], as_float(any_counts[0])));
     out.data.push_back(make_float4(rb[0], rb[1], rb[2], as_float(n_leaves == 2 ? pl.leaves[1].y : 0)));
-    out.data.push_back(make_float4(rb[3], rb[4], rb[5], 0.f));
+    out.data.push_back(make_float4(rb[3], rb[4], rb[5], as_float(any_counts[1])));
+    const auto pair_record = [&](int2 s) {
+        const int k = s.x, k1 = s.y < 0 ? k : s.y;
+        if (k < 0 || k >= n_records || k1 >= n_records) return false;  // (a layout of other leaves)
+        // the pair record of build_pairs_frames (csrc/nh_wavefront.hip), by the same float subtractions
+        const float4 a = prims[3 * (size_t)k], b = prims[3 * (size_t)k + 1], c = prims[3 * (size_t)k + 2];
+        const float4 a1 = prims[3 * (size_t)k1], b1 = prims[3 * (size_t)k1 + 1], c1 = prims[3 * (size_t)k1 + 2];
+        out.data.push_back(make_float4(a.x, a1.x, a.y, a1.y));
+        out.data.push_back(make_float4(a.z, a1.z, a.w, a1.w));
+        out.data.push_back(make_float4(b.x - a.x, b1.x - a1.x, b.y - a.y, b1.y - a1.y));
+        out.data.push_back(make_float4(b.z - a.z, b1.z - a1.z, c.x - a.x, c1.x - a1.x));
+        out.data.push_back(make_float4(c.y - a.y, c1.y - a1.y, c.z - a.z, c1.z - a1.z));
+        out.data.push_back(make_float4(c.w, c1.w, as_float(k), as_float(k1)));
+        return true;
+    };
     for (int l = 0; l < n_leaves; ++l) {
         const int2 p = pl.leaves[(size_t)l];
-        for (int i = 0, n = (p.y & 0xffff) + (p.y >> 16); i < n; ++i) {
-            const int2 s = pl.slots[(size_t)(p.x + i)];
-            const int k = s.x, k1 = s.y < 0 ? k : s.y;
-            if (k < 0 || k >= n_records || k1 >= n_records) return FlatImage{};  // (a layout of other leaves)
-            // the pair record of build_pairs_frames (csrc/nh_wavefront.hip), by the same float subtractions
-            const float4 a = prims[3 * (size_t)k], b = prims[3 * (size_t)k + 1], c = prims[3 * (size_t)k + 2];
-            const float4 a1 = prims[3 * (size_t)k1], b1 = prims[3 * (size_t)k1 + 1], c1 = prims[3 * (size_t)k1 + 2];
-            out.data.push_back(make_float4(a.x, a1.x, a.y, a1.y));
-            out.data.push_back(make_float4(a.z, a1.z, a.w, a1.w));
-            out.data.push_back(make_float4(b.x - a.x, b1.x - a1.x, b.y - a.y, b1.y - a1.y));
-            out.data.push_back(make_float4(b.z - a.z, b1.z - a1.z, c.x - a.x, c1.x - a1.x));
-            out.data.push_back(make_float4(c.y - a.y, c1.y - a1.y, c.z - a.z, c1.z - a1.z));
-            out.data.push_back(make_float4(c.w, c1.w, as_float(k), as_float(k1)));
-        }
+        for (int i = 0, n = (p.y & 0xffff) + (p.y >> 16); i < n; ++i)
+            if (!pair_record(pl.slots[(size_t)(p.x + i)])) return FlatImage{};
+    }
+    if (any_list) {
+        // at its fixed offset, behind room for kFlatMaxPairs closest-hit records (the unused ones zero)
+        out.data.resize((size_t)nhd::kFlatHeaderF4 + (size_t)nhd::kPairF4 * nhd::kFlatMaxPairs, make_float4(0.f, 0.f, 0.f, 0.f));
+        for (int l = 0; l < n_leaves; ++l)
+            for (const int2 &s : any_slots[l])
+                if (!pair_record(s)) return FlatImage{};
     }
     out.flat = true;
     return out;
@@ -664,8 +696,9 @@ FlatImage flat_image(const float boxes[18], const i2 *leaves, int n_leaves, cons
 
 extern "C" {
 
-int nh_flat_image(const float *records, int32_t n_records, const int32_t *leaves, int32_t n_leaves, const float *boxes,
-                  int32_t allowed, float *image, int32_t image_cap_f4, int32_t *n_f4, int32_t *box_equal) {
+int nh_flat_image_any(const float *records, int32_t n_records, const int32_t *leaves, int32_t n_leaves,
+                      const float *boxes, int32_t allowed, uint64_t any_word, float *image, int32_t image_cap_f4,
+                      int32_t *n_f4, int32_t *box_equal) {
     bool ok = n_records >= 0 && n_leaves >= 0 && (n_records == 0 || records) && (n_leaves == 0 || leaves) && boxes &&
               n_f4 && box_equal && image_cap_f4 >= 0 && (image_cap_f4 == 0 || image);
     std::vector<char> used((size_t)std::max(n_records, 0), 0);  // (as nh_pair_layout)
@@ -684,7 +717,8 @@ int nh_flat_image(const float *records, int32_t n_records, const int32_t *leaves
     const nh::i2 *lv = reinterpret_cast<const nh::i2 *>(leaves);
     const nh::f4 *rec = reinterpret_cast<const nh::f4 *>(records);
     const nh::PairLayout pl = nh::pair_layout(lv, n_leaves, rec, n_records, true);
-    const nh::FlatImage fi = nh::flat_image(boxes, lv, n_leaves, rec, n_records, pl, allowed != 0 && nh::flat_trace_knob());
+    const nh::FlatImage fi = nh::flat_image(boxes, lv, n_leaves, rec, n_records, pl, allowed != 0 && nh::flat_trace_knob(),
+                                            nh::any_list_knob() ? any_word : ~(uint64_t)0);
     *n_f4 = fi.flat ? (int32_t)fi.data.size() : 0;
     *box_equal = fi.box_equal;
     if (fi.flat) {
@@ -695,6 +729,12 @@ int nh_flat_image(const float *records, int32_t n_records, const int32_t *leaves
         std::memcpy(image, fi.data.data(), fi.data.size() * sizeof(nh::f4));
     }
     return NH_OK;
+}
+
+int nh_flat_image(const float *records, int32_t n_records, const int32_t *leaves, int32_t n_leaves, const float *boxes,
+                  int32_t allowed, float *image, int32_t image_cap_f4, int32_t *n_f4, int32_t *box_equal) {
+    return nh_flat_image_any(records, n_records, leaves, n_leaves, boxes, allowed, ~(uint64_t)0, image, image_cap_f4, n_f4,
+                             box_equal);
 }
 
 int nh_pair_layout(const float *records, int32_t n_records, const int32_t *leaves, int32_t n_leaves, int32_t by_kind,

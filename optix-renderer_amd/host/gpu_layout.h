@@ -77,6 +77,14 @@ bool primary_mask_in_front(const nh_camera &cam, const f4 *prims, int n_records,
 // The emitter-side word: bit k clear when no shadow ray of any bounce can be accepted by record k (all ones with more
 // than 64 records).
 uint64_t shadow_emitter_mask(const f4 *prims, int n_records, const float *emit_faces, int n_faces);
+// The scene-wide any-hit word: the emitter-side word less the supporting walls -- triangle records that have every
+// emitter vertex well in front of their plane and every possible far end of a shadow ray (a float hit point on any
+// record, of a ray from the camera or from another such point) on that same closed side, so that the ray ends, kEps
+// short of the far end, before their float test can accept it. Bit k set: record k stays. All ones where
+// shadow_emitter_mask is.
+uint64_t shadow_any_word(const nh_camera &cam, const f4 *prims, int n_records, const float *emit_faces, int n_faces);
+// NH_ANY_LIST=0 (read at every call; the BVH upload calls it once): the flat image gets no any-hit section
+bool any_list_knob();
 // The emit_faces of a scene: every emitting face's vertices when every emitter is an area light on a mesh without vertex
 // normals; empty otherwise (a point, spot, directional or envmap light, a sphere light, a mesh light with normals).
 std::vector<float> shadow_emitter_faces(const nh_scene_desc &d);
@@ -110,13 +118,19 @@ PairLayout pair_layout(const i2 *leaves, int n_leaves, const f4 *prims, int n_re
 //   data:  the image (empty when not flat); its pair records hold what the device computes for the LDS image's: p0, the
 //          edges p1 - p0 and p2 - p0 by the same IEEE subtractions, the flag words and the record indices
 //   box_equal: kFlatLeftEq / kFlatRightEq bits -- the child's six bounds have the bit patterns of the root's
+//   any_word: the scene-wide any-hit word (shadow_any_word; bit k set: record k stays). Unless it is all ones over the
+//          records, the image gets an any-hit section (any_list): at kFlatHeaderF4 + kPairF4 * kFlatMaxPairs, each
+//          leaf's kept records paired again by pair_layout's rules, the left leaf's first; header words [3].w / [5].w
+//          hold each leaf's counts (triangle pairs | sphere pairs << 16) and [0].w the kFlatAnyList bit. box_equal
+//          does not hold that bit.
 struct FlatImage {
     bool flat = false;
+    bool any_list = false;
     int box_equal = 0;
     std::vector<f4> data;
 };
 FlatImage flat_image(const float boxes[18], const i2 *leaves, int n_leaves, const f4 *prims, int n_records,
-                     const PairLayout &pl, bool allowed);
+                     const PairLayout &pl, bool allowed, uint64_t any_word = ~(uint64_t)0);
 // NH_FLAT_TRACE=0 (read at every call; the BVH upload calls it once) turns flat traversal off
 bool flat_trace_knob();
 

@@ -8,8 +8,11 @@
 //   - the emitter-side word (valid at every bounce): the records that lie wholly behind every emitter face's plane;
 //   - one word per 32x32 image block (bounce 0, pinhole camera): the records whose box comes near the box of the
 //     emitter faces and of what the block's camera rays can hit first, less the records the first word leaves out.
-// The kernels read the per-block words only (rr_step<.., SMASK>); on its own at the later bounces the emitter-side word
-// did not pay.
+// At run time the kernels read the per-block words only (rr_step<.., SMASK>): tested per pair at the later bounces the
+// emitter-side word did not pay. Its static use is the third result, the scene-wide any-hit word: the
+// emitter-side word less the supporting walls (supporting_walls below), decided once at upload; the flat image gets
+// pair records of their own for the records it keeps (gpu_layout.cpp flat_image), which every any-hit query of the
+// flat bounce kernels loops over instead of all records.
 // Both rest on one bound per record, rho: whenever the float test of record K accepts a ray that starts on an emitter
 // face with maxt no longer than the scene, the exact ray passes within rho_K of K at a parameter within rho_K of
 // [0, maxt]. DESIGN.md has the derivation; the constants below are its.
@@ -17,6 +20,7 @@
 // Plain C++ (no HIP): part of both libraries; checked on the CPU by tests/test_shadow_masks_host.py.
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 
 #include "gpu_layout.h"
@@ -66,6 +70,9 @@ struct Record {
     double sin_t;   // triangle: sine of the angle between its edges e1, e2
     double len;     // triangle: the longer of e1, e2
     double rho;     // the bound of the header; INFINITY: the record is never left out
+    double s;       // triangle with a finite rho: the emitter vertices' least distance from its plane, less eps_o
+    int side;       // ... and the side of the plane they lie on (+1: the normal's)
+    double reach;   // ... and the largest distance from an emitter vertex to one of its vertices
     double grown;   // sphere: half side of its grown box (rho = grown - r)
     AABB box;       // the record's own box
 };
@@ -85,9 +92,66 @@ struct Analysis {
     AABB scene, emit;
     double eps_o = 0, eta = 0, d_e = 0, m = 0;
     uint64_t emitter_word = ~(uint64_t)0;
+    uint64_t any_word = ~(uint64_t)0;  // the emitter-side word less the supporting walls
 };
 
-Analysis analyse(const f4 *prims, int n_records, const float *emit_faces, int n_faces) {
+const double kEpsD = 1e-4f;  // kEps (csrc/nh_device.h): a shadow ray ends this far short of the path vertex
+
+// The supporting-wall rule ("The any-hit list"): bit k clear when triangle record k has every
+// emitter vertex at least s in front of its plane and every possible far end of a shadow ray -- a float hit point on any
+// record -- on that closed side up to eps_f, with the bound closing: the ray from an emitter point p to a far end ref
+// crosses K's plane no earlier than |ref - p| s / (s + eps_f), the float t is within rho_t of that, and the ray ends
+// kEps before ref. A far end on a triangle record is the float barycentric point (within hit_round of the record); on
+// a sphere it is o + t d with the float root t, within g_hit of the centre (the residual of the float root in
+// |o + t d - c|^2 - r^2 is at most 64u far^2, far the longest ray that can reach the sphere), of whose box every
+// corner is taken. An emitter's own record has s = 0 and stays; a sphere always stays.
+uint64_t supporting_walls(const Analysis &A, int n_records, const V3 *origin, double origin_radius) {
+    uint64_t keep = ~(uint64_t)0;
+    if (!A.ok) return keep;
+    AABB from = A.scene;  // where rays start that end on a record: path vertices, emitter points, the camera
+    if (origin) {
+        from.add(V3{origin->x - origin_radius, origin->y - origin_radius, origin->z - origin_radius});
+        from.add(V3{origin->x + origin_radius, origin->y + origin_radius, origin->z + origin_radius});
+    }
+    if (!std::isfinite(from.lo.x + from.lo.y + from.lo.z + from.hi.x + from.hi.y + from.hi.z)) return keep;
+    double max_abs = 0;
+    for (const V3 &q : {from.lo, from.hi}) max_abs = std::max({max_abs, std::fabs(q.x), std::fabs(q.y), std::fabs(q.z)});
+    const double hit_round = 8.0 * kU * max_abs;
+    std::vector<V3> ends;  // the far ends' hull: every triangle vertex, every corner of a sphere's hit box
+    for (const Record &R : A.rec) {
+        if (!R.sphere) {
+            ends.insert(ends.end(), R.p, R.p + 3);
+            continue;
+        }
+        double far_d = 0;
+        for (int i = 0; i < 8; ++i) {
+            const V3 q{i & 1 ? from.hi.x : from.lo.x, i & 2 ? from.hi.y : from.lo.y, i & 4 ? from.hi.z : from.lo.z};
+            far_d = std::max(far_d, norm(q - R.p[0]) + R.r);
+        }
+        if (!(R.r > 0.0)) return keep;
+        const double g_hit = R.r + 64.0 * kU * far_d * far_d / R.r + hit_round;
+        for (int i = 0; i < 8; ++i)
+            ends.push_back(V3{R.p[0].x + (i & 1 ? g_hit : -g_hit), R.p[0].y + (i & 2 ? g_hit : -g_hit),
+                              R.p[0].z + (i & 4 ? g_hit : -g_hit)});
+    }
+    for (int k = 0; k < n_records; ++k) {
+        const Record &R = A.rec[(size_t)k];
+        if (R.sphere || !std::isfinite(R.rho)) continue;  // (finite rho: one side, s > 0, s sin >= 32u R)
+        double depth = 0;
+        for (const V3 &q : ends) depth = std::max(depth, -R.side * dot(R.n, q - R.p[0]));
+        const double eps_f = depth + hit_round;
+        const double rho_t = 8.0 * kU * A.d_e * (R.reach + 2.0 * A.d_e) / (R.s * R.sin_t);
+        // (a crossing behind the origin lies at t <= -s: the float t stays negative)
+        if (!(R.s > 2.0 * rho_t) || !(kEpsD > 2.0 * (A.d_e * eps_f / R.s + rho_t + 4.0 * kU * A.d_e))) continue;
+        keep &= ~((uint64_t)1 << k);
+    }
+    return keep;
+}
+
+// origin: where a path's first ray starts (the camera: the supporting-wall rule's far ends include its rays' hits) and
+// how far from that point at most (a lens); null: no such ray
+Analysis analyse(const f4 *prims, int n_records, const float *emit_faces, int n_faces, const V3 *origin = nullptr,
+                 double origin_radius = 0.0) {
     Analysis A;
     if (n_records <= 0 || n_records > 64 || n_faces <= 0 || !emit_faces) return A;
     double min_sin = 1.0, max_abs = 0.0;
@@ -174,6 +238,9 @@ Analysis analyse(const f4 *prims, int n_records, const float *emit_faces, int n_
         // (the second condition: the numerator of t keeps its sign and three quarters of its size in float)
         if (!one_side || !(s > 0.0) || !(32.0 * kU * reach <= s * R.sin_t)) continue;
         R.rho = 64.0 * kU * (reach + R.len + A.d_e) * A.d_e / (s * R.sin_t);
+        R.s = s;
+        R.side = side;
+        R.reach = reach;
     }
     A.ok = true;
     // the emitter-side word: record k is left out when it lies behind every face's plane by more than delta_k
@@ -197,6 +264,23 @@ Analysis analyse(const f4 *prims, int n_records, const float *emit_faces, int n_
         if (!behind) word |= (uint64_t)1 << k;
     }
     A.emitter_word = word;
+    // The any-hit word, for the scene as a whole: the emitters stand in an enclosure -- every triangle record that is
+    // not an emitter's own is left out by one of the two rules -- or nothing is left out. (A triangle that neither rule
+    // can place is the sign of a scene the rules were not made for: a mesh through or outside a wall, a light on a wall.)
+    A.any_word = word & supporting_walls(A, n_records, origin, origin_radius);
+    for (int k = 0; k < n_records; ++k) {
+        const Record &R = A.rec[(size_t)k];
+        if (R.sphere || !((A.any_word >> k) & 1)) continue;
+        bool own = false;  // its three vertices are a face's (the records and the faces hold the same floats)
+        for (const Face &F : A.faces) {
+            int hit = 0;
+            for (int i = 0; i < 3; ++i)
+                for (int j = 0; j < 3; ++j)
+                    hit += R.p[i].x == F.p[j].x && R.p[i].y == F.p[j].y && R.p[i].z == F.p[j].z;
+            own = own || hit >= 3;
+        }
+        if (!own) A.any_word = ~(uint64_t)0;
+    }
     return A;
 }
 
@@ -239,6 +323,19 @@ std::vector<float> shadow_emitter_faces(const nh_scene_desc &d) {
 
 uint64_t shadow_emitter_mask(const f4 *prims, int n_records, const float *emit_faces, int n_faces) {
     return analyse(prims, n_records, emit_faces, n_faces).emitter_word;
+}
+
+uint64_t shadow_any_word(const nh_camera &cam, const f4 *prims, int n_records, const float *emit_faces, int n_faces) {
+    const float *cw = cam.camera_to_world;
+    const V3 org{(double)cw[3] / cw[15], (double)cw[7] / cw[15], (double)cw[11] / cw[15]};
+    const double lens = std::fabs((double)cam.lens_radius);
+    if (!std::isfinite(org.x + org.y + org.z + lens)) return ~(uint64_t)0;
+    return analyse(prims, n_records, emit_faces, n_faces, &org, lens).any_word;
+}
+
+bool any_list_knob() {
+    const char *e = std::getenv("NH_ANY_LIST");
+    return !(e && e[0] == '0');
 }
 
 bool shadow_block_masks(const nh_camera &cam, const f4 *prims, int n_records, const float *emit_faces, int n_faces,
@@ -391,6 +488,16 @@ int nh_shadow_masks(const nh_camera *camera, const float *records, int32_t n_rec
     std::vector<uint64_t> m;
     *built = nh::shadow_block_masks(*camera, prims, n_records, emit_faces, n_emit_faces, blocks, n_blocks, m) ? 1 : 0;
     if (*built && n_blocks > 0) std::memcpy(masks, m.data(), (size_t)n_blocks * sizeof(uint64_t));
+    return NH_OK;
+}
+
+int nh_shadow_any_word(const nh_camera *camera, const float *records, int32_t n_records, const float *emit_faces,
+                       int32_t n_emit_faces, uint64_t *word) {
+    if (!camera || !word || n_records < 0 || (n_records > 0 && !records) || (n_emit_faces > 0 && !emit_faces)) {
+        nh::set_host_error("nh_shadow_any_word: invalid argument");
+        return NH_ERR_INVALID;
+    }
+    *word = nh::shadow_any_word(*camera, reinterpret_cast<const nh::f4 *>(records), n_records, emit_faces, n_emit_faces);
     return NH_OK;
 }
 

@@ -205,7 +205,7 @@ class nh_render_stats(C.Structure):
                                   "tail_coop_bounces", "bounce_cycles_load", "bounce_cycles_body",
                                   "bounce_cycles_shadow", "bounce_cycles_closest", "bounce_cycles_head",
                                   "bounce_cycles_store", "bounce_bounces", "bounce_traits", "primary_masks",
-                                  "pair_kinds", "flat_trace", "shadow_masks")]
+                                  "pair_kinds", "flat_trace", "shadow_masks", "any_list")]
 
 
 def _sig(name, res, *args):
@@ -242,6 +242,9 @@ _sig("nh_shadow_masks", _i32, C.POINTER(nh_camera), _fp, _i32, _fp, _i32, C.POIN
      C.POINTER(C.c_uint64), C.POINTER(_i32))
 _sig("nh_pair_layout", _i32, _fp, _i32, C.POINTER(_i32), _i32, _i32, C.POINTER(_i32), C.POINTER(_i32))
 _sig("nh_flat_image", _i32, _fp, _i32, C.POINTER(_i32), _i32, _fp, _i32, _fp, _i32, C.POINTER(_i32), C.POINTER(_i32))
+_sig("nh_shadow_any_word", _i32, C.POINTER(nh_camera), _fp, _i32, _fp, _i32, C.POINTER(C.c_uint64))
+_sig("nh_flat_image_any", _i32, _fp, _i32, C.POINTER(_i32), _i32, _fp, _i32, C.c_uint64, _fp, _i32, C.POINTER(_i32),
+     C.POINTER(_i32))
 _sig("nh_framebuffer_to_rgb", _i32, _fp, _i32, _i32, _i32, _fp)
 _sig("nh_write_pfm", _i32, C.c_char_p, _fp, _i32, _i32)
 _sig("nh_image_load_png", _i32, C.c_char_p, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(_i32), C.POINTER(_i32))
@@ -985,19 +988,38 @@ def pair_layout(records: np.ndarray, leaves, by_kind: bool = True):
     return slots, lp
 
 
-def flat_image(records: np.ndarray, leaves, boxes, allowed: bool = True):
+def shadow_any_word(camera: nh_camera, records: np.ndarray, emit_faces) -> int:
+    """nh_shadow_any_word: the scene-wide any-hit word, an int whose clear bit k says no shadow ray of any bounce can be
+    accepted by record k (the emitter-side word's zeros and the supporting walls); all ones: nothing is left out.
+    emit_faces: as for shadow_masks."""
+    rec = np.ascontiguousarray(records, dtype=np.float32).reshape(-1, 12)
+    ef = np.zeros((0, 9), np.float32) if emit_faces is None else np.ascontiguousarray(emit_faces, np.float32).reshape(-1, 9)
+    word = C.c_uint64(0)
+    _host_check(_lib.nh_shadow_any_word(C.byref(camera), _fptr(rec), len(rec), _fptr(ef), len(ef), C.byref(word)),
+                "shadow_any_word")
+    return int(word.value)
+
+
+def flat_image(records: np.ndarray, leaves, boxes, allowed: bool = True, any_word: int | None = None):
     """nh_flat_image: the flat image of a tree of one leaf or of a root with two leaves -- `leaves` its (start, count)
     rows, `boxes` the root's, left child's and right child's boxes (18 floats: min xyz, max xyz each). Returns (image,
     box_equal): image (n, 4) float32 -- 6 header rows, then 6 rows per pair record -- or None when the scene is not flat;
-    box_equal bit 0 / 1: the left / right child's box is bit-equal to the root's."""
+    box_equal bit 0 / 1: the left / right child's box is bit-equal to the root's. any_word (nh_flat_image_any): the
+    scene-wide any-hit word; unless it keeps every record the image has an any-hit section from row 6 + 6 * 16 on."""
     rec = np.ascontiguousarray(records, dtype=np.float32).reshape(-1, 12)
     lv = np.ascontiguousarray(leaves, dtype=np.int32).reshape(-1, 2)
     bx = np.ascontiguousarray(boxes, dtype=np.float32).ravel()
     assert bx.size == 18
-    cap = 6 + 6 * 16
+    cap = 6 + 6 * 16 * (1 if any_word is None else 2)
     img, n, eq = np.zeros((cap, 4), np.float32), _i32(0), _i32(0)
-    _host_check(_lib.nh_flat_image(_fptr(rec), len(rec), lv.ctypes.data_as(C.POINTER(_i32)), len(lv), _fptr(bx),
-                                   1 if allowed else 0, _fptr(img), cap, C.byref(n), C.byref(eq)), "flat_image")
+    ip = lv.ctypes.data_as(C.POINTER(_i32))
+    if any_word is None:
+        _host_check(_lib.nh_flat_image(_fptr(rec), len(rec), ip, len(lv), _fptr(bx), 1 if allowed else 0, _fptr(img), cap,
+                                       C.byref(n), C.byref(eq)), "flat_image")
+    else:
+        _host_check(_lib.nh_flat_image_any(_fptr(rec), len(rec), ip, len(lv), _fptr(bx), 1 if allowed else 0,
+                                           C.c_uint64(any_word & ((1 << 64) - 1)), _fptr(img), cap, C.byref(n),
+                                           C.byref(eq)), "flat_image_any")
     return (img[:n.value].copy() if n.value else None), int(eq.value)
 
 
