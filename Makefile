@@ -22,10 +22,10 @@ HIP_FLAGS  := -std=c++17 -O3 -fPIC --offload-arch=$(ARCH) $(FP_FLAGS) \
 
 HOST_SRC := $(PKG)/host/xml_lite.cpp $(PKG)/host/scene_loader.cpp $(PKG)/host/bvh_build.cpp $(PKG)/host/image_io.cpp \
             $(PKG)/host/png_decode.cpp $(PKG)/host/hdr_decode.cpp $(PKG)/host/gpu_layout.cpp $(PKG)/host/ttest.cpp \
-            $(PKG)/host/photon_host.cpp $(PKG)/host/primary_masks.cpp $(PKG)/host/shadow_masks.cpp
+            $(PKG)/host/photon_host.cpp $(PKG)/host/primary_masks.cpp $(PKG)/host/shadow_masks.cpp $(PKG)/host/chi2test.cpp
 HIP_SRC  := $(PKG)/csrc/nh_kernels.hip $(PKG)/csrc/nh_denoise.hip $(PKG)/csrc/nh_splat.hip $(PKG)/csrc/nh_api.hip \
             $(PKG)/csrc/nh_upload.hip $(PKG)/csrc/nh_pipeline.hip $(PKG)/csrc/nh_adaptive_api.hip $(PKG)/csrc/nh_query_api.hip \
-            $(PKG)/csrc/nh_photon_api.hip $(PKG)/csrc/nh_av.hip
+            $(PKG)/csrc/nh_photon_api.hip $(PKG)/csrc/nh_av.hip $(PKG)/csrc/nh_chi2_api.hip
 HOST_OBJ := $(patsubst $(PKG)/host/%.cpp,$(OBJDIR)/host_%.o,$(HOST_SRC))
 # nh_wavefront.hip is compiled as five translation units (-DNH_WF_PART=k, each instantiating its own kernels) so
 # its kernels build in parallel
@@ -39,12 +39,13 @@ HIP_OBJ  := $(patsubst $(PKG)/csrc/%.hip,$(OBJDIR)/hip_%.o,$(HIP_SRC)) \
 # part 4 (the diffuse area-light instantiations) have no variant, and parts 1 and 2 leave their other kernels out.
 # nh_volume.hip (the volumetric path tracers and the medium query) is built this way only: one copy, with every BSDF
 # and emitter type. So are nh_adaptive.hip (the adaptive sampler's kernels) and nh_query.hip (the radiance query and the
-# t-test estimators) and nh_photon.hip (the photon mapper's passes). The integrators themselves are device
-# function templates in headers (nh_integrators.h, nh_volume.h), shared by these units.
+# t-test estimators), nh_photon.hip (the photon mapper's passes) and nh_chi2.hip (the chi^2 test's histogram and
+# expected-frequency kernels). The integrators themselves are device function templates in headers
+# (nh_integrators.h, nh_volume.h), shared by these units.
 DZ_PARTS := 1 2
 HIP_OBJ  += $(OBJDIR)/hipdz_nh_kernels.o $(OBJDIR)/hipdz_nh_disney.o $(OBJDIR)/hipdz_nh_emitter_query.o \
             $(OBJDIR)/hipdz_nh_volume.o $(OBJDIR)/hipdz_nh_adaptive.o $(OBJDIR)/hipdz_nh_query.o \
-            $(OBJDIR)/hipdz_nh_photon.o \
+            $(OBJDIR)/hipdz_nh_photon.o $(OBJDIR)/hipdz_nh_chi2.o \
             $(foreach k,$(DZ_PARTS),$(OBJDIR)/hipdz_nh_wavefront_p$(k).o)
 HIP_DEPS := $(wildcard $(PKG)/csrc/*.h) $(PKG)/host/gpu_layout.h include/nori_hip.h
 # The wavefront kernels build without LLVM's machine-level LICM: it hoists loop invariants out of the traversal, bounce
@@ -65,8 +66,9 @@ MANUAL   := tests/c/bin/manual_scene
 LAYOUTCHECK := tests/c/bin/gpu_layout_check
 DISPATCHCHECK := tests/c/bin/dispatch_check
 FLATCHECK := tests/c/bin/flat_combine_check
+SIMPSONCHECK := tests/c/bin/simpson_check
 
-all: $(LIB) $(HOSTLIB) $(ORACLE) $(CLI) $(RCPCHECK) $(VALUBENCH) $(MANUAL) $(LAYOUTCHECK) $(DISPATCHCHECK) $(FLATCHECK)
+all: $(LIB) $(HOSTLIB) $(ORACLE) $(CLI) $(RCPCHECK) $(VALUBENCH) $(MANUAL) $(LAYOUTCHECK) $(DISPATCHCHECK) $(FLATCHECK) $(SIMPSONCHECK)
 
 # C test: a scene description filled field by field (no XML loader), rendered through the C-ABI and
 # compared with the oracle (run by tests/test_gpu_parity.py)
@@ -90,6 +92,12 @@ $(DISPATCHCHECK): tests/c/dispatch_check.cpp $(PKG)/csrc/nh_dispatch.h
 # C++ test: the combine step of the flat two-leaf traversal (csrc/nh_flat_combine.h) on the CPU, no HIP (run by
 # tests/test_flat_combine_host.py)
 $(FLATCHECK): tests/c/flat_combine_check.cpp $(PKG)/csrc/nh_flat_combine.h
+	@mkdir -p tests/c/bin
+	$(CXX) -std=c++17 -O2 -Wall -Wextra $(FP_FLAGS) -I$(PKG)/csrc -o $@ $<
+
+# C++ test: the iterative adaptive Simpson rule (csrc/nh_simpson.h) on the CPU against the recursion, no HIP (run by
+# tests/test_simpson_host.py)
+$(SIMPSONCHECK): tests/c/simpson_check.cpp $(PKG)/csrc/nh_simpson.h
 	@mkdir -p tests/c/bin
 	$(CXX) -std=c++17 -O2 -Wall -Wextra $(FP_FLAGS) -I$(PKG)/csrc -o $@ $<
 

@@ -750,8 +750,8 @@ int nh_ttest_bsdf(nh_ctx *ctx, const nh_bsdf *bsdf, const float *albedo, float a
 /* StudentsTTest::execute on device `device`: every <scene> of the file loaded, built, uploaded and run through
  * nh_ttest_scene with the file's sampleCount (scene tests), or every <bsdf> x angle through nh_ttest_bsdf with
  * first_draw running on across the tests (BSDF tests), then nh_students_t_test with num_tests = the number of
- * references. Writes min(*n_results, cap) results. A chi2test file returns NH_ERR_UNSUPPORTED. Errors are reported
- * through nh_host_last_error. */
+ * references. Writes min(*n_results, cap) results. A chi2test file returns NH_ERR_UNSUPPORTED here: nh_chi2_run
+ * (below) is its entry point. Errors are reported through nh_host_last_error. */
 typedef struct nh_test_result {
     double mean, variance, reference, p_value;
     int32_t accepted;
@@ -761,6 +761,68 @@ typedef struct nh_test_result {
 } nh_test_result;
 int nh_test_run(int device, const char *path, uint64_t seed, nh_test_result *results, int32_t cap,
                 int32_t *n_results);
+
+/* ---- the reference's chi^2 test procedure (src/utils/chi2test.cpp) --------------------- */
+
+/* ChiSquareTest's constructor properties (chi2test.cpp:45-74), beside nh_test_desc: resolution [10] (the cos(theta)
+ * cells; phi takes twice as many), minExpFrequency [5], testCount [5] and sampleCount resolved (-1, or any negative
+ * value: resolution * 2 resolution * 5000; nh_test_desc keeps the file's own value). NH_ERR_INVALID for a ttest. */
+typedef struct nh_chi2_params {
+    int32_t resolution;
+    int32_t min_exp_frequency;
+    int32_t test_count;
+    int32_t sample_count;
+} nh_chi2_params;
+int nh_test_get_chi2_params(const nh_test *test, nh_chi2_params *out);
+
+/* largest contingency table of nh_chi2_histogram: one uint32 per cell in 32 KB of LDS */
+#define NH_CHI2_MAX_CELLS 8192
+/* largest n_wi * cells of one nh_chi2_expected call */
+#define NH_CHI2_EXPECTED_MAX (1 << 20)
+/* ChiSquareTest's sampling loop (chi2test.cpp:163-181) on the device: sample k takes draws first_draw + 2k (x) and
+ * first_draw + 2k + 1 (y) of the default-state pcg32, as nh_ttest_bsdf does; a sample whose weight is all zero is
+ * skipped; the others count into cell cosThetaBin * res_phi + phiBin, the bins formed in fp32 as the reference writes
+ * them. obs: res_theta * res_phi doubles (the reference's obsFrequencies), whole counts, the same bits on every run
+ * (integer atomics only). wi: the incident direction in the BSDF's frame; albedo as in nh_bsdf_query.
+ * 1 <= n <= INT32_MAX. NH_ERR_UNSUPPORTED for a resolution below 1 or more than NH_CHI2_MAX_CELLS cells. Needs no
+ * uploaded scene. */
+int nh_chi2_histogram(nh_ctx *ctx, const nh_bsdf *bsdf, const float *albedo, const float *wi, uint64_t first_draw,
+                      int32_t n, int32_t res_theta, int32_t res_phi, double *obs);
+/* The expected frequencies (chi2test.cpp:186-214) of n_wi incident directions (wi: 3 n_wi floats) in one launch: per
+ * (wi, cell) hypothesis::adaptiveSimpson2D (eps 1e-6, depth 6) of the device's bsdf_pdf in the solid-angle measure
+ * over the cell's cos(theta) x phi rectangle -- the phi bounds evaluated in fp32 as the reference's float M_PI makes
+ * them -- times (double)sample_count. exp: n_wi * cells doubles; evals (n_wi * cells, may be NULL): the pdf
+ * evaluations each cell took. The integrator is csrc/nh_simpson.h, the recursion's own summation order. */
+int nh_chi2_expected(nh_ctx *ctx, const nh_bsdf *bsdf, const float *albedo, int32_t n_wi, const float *wi,
+                     int32_t res_theta, int32_t res_phi, int32_t sample_count, double *exp, uint32_t *evals);
+/* hypothesis::chi2_test (ext/hypothesis/hypothesis.h:140-235): the cells sorted by expected frequency (ties by cell
+ * index: a stable order, where std::sort's is unspecified), pooled as its two pooling branches say, Pearson's
+ * statistic, dof - 1, p = 1 - chi2_cdf, the Sidak-corrected level; *accepted = 0 when p < level or p is not finite.
+ * *kind tells the rejections apart; on NH_CHI2_REJECTED_ZERO_CELL *statistic is the observed count of the offending
+ * cell and *p_value NaN, on NH_CHI2_REJECTED_DOF *p_value is NaN. Every out pointer but accepted may be NULL.
+ * NH_ERR_INVALID for n_cells < 1 or num_tests < 1. Host only. */
+enum { NH_CHI2_ACCEPTED = 0, NH_CHI2_REJECTED_P_VALUE = 1, NH_CHI2_REJECTED_ZERO_CELL = 2, NH_CHI2_REJECTED_DOF = 3 };
+int nh_chi2_test(int32_t n_cells, const double *obs, const double *exp, int32_t sample_count,
+                 double min_exp_frequency, double alpha, int32_t num_tests, int32_t *accepted, double *p_value,
+                 double *statistic, int32_t *dof, int32_t *pooled_cells, int32_t *kind);
+/* ChiSquareTest::execute (chi2test.cpp:131-234) on device `device`: one default-state pcg32 runs through the file;
+ * test T (over <bsdf> x testCount) draws cosTheta and phi of its wi at draws T (2 + 2n), + 1 and its n samples from
+ * draw T (2 + 2n) + 2 (nh_chi2_histogram); the expected frequencies of every test come from one nh_chi2_expected
+ * launch per <bsdf>; nh_chi2_test with num_tests = testCount * the number of <bsdf>. Writes min(*n_results, cap)
+ * results. tables (may be NULL): per written result 2 * cells doubles, the observed then the expected frequencies.
+ * A ttest file returns NH_ERR_INVALID, a textured <bsdf> NH_ERR_UNSUPPORTED. Errors through nh_host_last_error. */
+typedef struct nh_chi2_result {
+    double statistic;             /* chi^2 (NH_CHI2_REJECTED_ZERO_CELL: the offending cell's observed count) */
+    double p_value, level;        /* level: the Sidak-corrected significance level */
+    double obs_sum, exp_sum;      /* sums of the two tables, in cell order */
+    float wi[3];
+    int32_t dof, pooled_cells;
+    int32_t accepted, kind;       /* kind: NH_CHI2_* */
+    int32_t sample_count;
+} nh_chi2_result;
+int nh_chi2_run(int device, const char *path, nh_chi2_result *results, int32_t cap, int32_t *n_results);
+int nh_chi2_run_tables(int device, const char *path, nh_chi2_result *results, int32_t cap, int32_t *n_results,
+                       double *tables);
 
 /* ---- the photon mapper (src/integrators/photonmapper.cpp) ------------------------------- */
 

@@ -489,3 +489,33 @@ void launch_ttest_reduce(const float *lum, int n, const double *center, double d
                          hipStream_t st);
 }  // namespace nh
 }  // namespace nh_disney
+
+// ---- the chi^2 test's two tables (nh_chi2.hip, driven by nh_chi2_api.hip) ----
+// ChiSquareTest's sampling loop: lane l owns samples [l run, (l + 1) run) of the n, sample j at draws first_draw + 2j,
+// + 2j + 1 of the default-state pcg32. counts: res_theta * res_phi uint32, zeroed by the caller
+struct Chi2Hist {
+    uint64_t first_draw;
+    int n, run;
+    int res_theta, res_phi;
+    int sub_tables;  // 1: every wave of a workgroup counts into its own LDS table (kChi2Block / 64 of them fit)
+    nhd::DBsdf bsdf;
+    float albedo[3], wi[3];
+    uint32_t *counts;
+};
+// The expected frequencies: entry w * cells + cell of exp / evals is cell `cell` of incident direction wi[3w..3w + 2]
+struct Chi2Expected {
+    int n_wi, res_theta, res_phi, sample_count;
+    nhd::DBsdf bsdf;
+    const float *wi;
+    double *exp;
+    uint32_t *evals;  // may be null
+};
+constexpr int kChi2Block = 256;        // lanes of a histogram workgroup
+constexpr int kChi2MinRun = 16;        // fewest samples a lane owns: one pcg_advance per run
+constexpr int kChi2MaxGroups = 2048;   // most workgroups of a histogram launch; beyond it the runs grow
+namespace nh_disney {
+namespace nh {
+void launch_chi2_histogram(const Chi2Hist &h, hipStream_t st);
+void launch_chi2_expected(const Chi2Expected &e, hipStream_t st);
+}  // namespace nh
+}  // namespace nh_disney

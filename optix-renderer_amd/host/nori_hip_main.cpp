@@ -10,7 +10,8 @@
 // of the per-path streams (default 0).
 // A file whose root is a <test type="ttest"> runs the reference's t-tests instead (StudentsTTest::execute,
 // src/utils/ttest.cpp): per test the sample mean, variance, t-statistic and verdict, then "Passed p/t tests."; the
-// exit status is 0 only if all passed.
+// exit status is 0 only if all passed. A <test type="chi2test"> root runs the reference's chi^2 tests
+// (ChiSquareTest::execute, src/utils/chi2test.cpp) the same way.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -55,6 +56,46 @@ static int run_tests(const std::string &path, const nh_test *test, int device, u
     return passed == n ? 0 : 1;
 }
 
+// ChiSquareTest::execute's report (chi2test.cpp:147-233, hypothesis.h:163-234) for a <test type="chi2test"> file run
+// on the HIP path (nh_chi2_run); 0 only if every test passed. The chi2test_%i.m dumps are not written.
+static int run_chi2_tests(const std::string &path, const nh_test *test, int device) {
+    nh_test_desc td;
+    nh_chi2_params cp;
+    nh_test_get_desc(test, &td);
+    if (nh_test_get_chi2_params(test, &cp)) return die("test", nh_host_last_error());
+    const size_t n_tests = (size_t)td.n_bsdfs * (size_t)(cp.test_count > 0 ? cp.test_count : 0);
+    std::vector<nh_chi2_result> res(n_tests ? n_tests : 1);
+    int32_t n = 0;
+    if (nh_chi2_run(device, path.c_str(), res.data(), (int32_t)res.size(), &n)) return die("test", nh_host_last_error());
+    int passed = 0;
+    for (int i = 0; i < n && i < (int)res.size(); ++i) {
+        const nh_chi2_result &r = res[i];
+        std::printf("------------------------------------------------------\n");
+        std::printf("Testing: BSDF %d (wi = [%g, %g, %g])\n", i / cp.test_count, r.wi[0], r.wi[1], r.wi[2]);
+        std::printf("Accumulating %d samples into a %dx%d contingency table .. done.\n", r.sample_count, cp.resolution,
+                    2 * cp.resolution);
+        std::printf("Integrating expected frequencies .. done.\n");
+        if (r.kind == NH_CHI2_REJECTED_ZERO_CELL) {
+            std::printf("Encountered %g samples in a cell with expected frequency 0. Rejecting the null hypothesis!\n\n",
+                        r.statistic);
+            continue;
+        }
+        if (r.pooled_cells > 0)
+            std::printf("Pooled %d to ensure sufficiently high expected cell frequencies (>%g)\n", r.pooled_cells,
+                        (double)cp.min_exp_frequency);
+        if (r.kind == NH_CHI2_REJECTED_DOF) {
+            std::printf("The number of degrees of freedom (%d) is too low!\n\n", r.dof);
+            continue;
+        }
+        std::printf("Chi^2 statistic = %g (d.o.f. = %d)\n", r.statistic, r.dof);
+        std::printf("%s the null hypothesis (p-value = %g, significance level = %g)\n\n",
+                    r.accepted ? "Accepted" : "***** Rejected *****", r.p_value, r.level);
+        passed += r.accepted ? 1 : 0;
+    }
+    std::printf("Passed %d/%d tests.\n", passed, (int)n);
+    return passed == n ? 0 : 1;
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) {
         std::fprintf(stderr, "usage: nori_hip scene.xml [--spp N] [--width W --height H] [--device D] [--ordered] [--pfm out] [--png] [--seed S]\n");
@@ -81,7 +122,10 @@ int main(int argc, char **argv) {
     nh_test *test = nullptr;
     const int trc = nh_test_load_xml(scene_path.c_str(), &test);
     if (trc == NH_OK) {
-        const int rc = run_tests(scene_path, test, device, seed);
+        nh_test_desc td;
+        nh_test_get_desc(test, &td);
+        const int rc = td.type == NH_TEST_CHI2TEST ? run_chi2_tests(scene_path, test, device)
+                                                   : run_tests(scene_path, test, device, seed);
         nh_test_free(test);
         return rc;
     }

@@ -1295,6 +1295,7 @@ struct TestData {
     std::vector<float> angles, references;
     uint32_t n_scenes = 0;
     std::vector<nh_bsdf> bsdfs;
+    nh_chi2_params chi2{10, 5, 5, -1};  // ChiSquareTest's own properties (chi2test.cpp:45-74)
 };
 
 TestData *load_test(const std::string &path) {
@@ -1310,6 +1311,15 @@ TestData *load_test(const std::string &path) {
     if (!chi2) {
         td->angles = float_list(p, "angles");
         td->references = float_list(p, "references");
+    } else {
+        td->chi2.resolution = p.get_int("resolution", 10);
+        td->chi2.min_exp_frequency = p.get_int("minExpFrequency", 5);
+        td->chi2.test_count = p.get_int("testCount", 5);
+        // chi2test.cpp:72-73, in 64 bits here: a resolution whose product leaves int32 stays negative and is refused
+        // where the table is (nh_chi2_histogram)
+        const int64_t res = td->chi2.resolution, automatic = res * (2 * res) * 5000;
+        td->chi2.sample_count = td->sample_count >= 0 ? td->sample_count
+                                : (automatic > 0 && automatic <= INT32_MAX ? (int32_t)automatic : -1);
     }
     SceneData scratch;  // the BSDF parser appends a textured BSDF's textures to a scene
     for (auto &ch : obj->children) {
@@ -1458,6 +1468,16 @@ int nh_test_get_desc(const nh_test *test, nh_test_desc *out) {
     out->n_scenes = t.n_scenes;
     out->n_bsdfs = (uint32_t)t.bsdfs.size();
     out->bsdfs = t.bsdfs.data();
+    return NH_OK;
+}
+
+int nh_test_get_chi2_params(const nh_test *test, nh_chi2_params *out) {
+    if (!test || !out) { nh::set_host_error("null argument"); return NH_ERR_INVALID; }
+    if (test->data->type != NH_TEST_CHI2TEST) {
+        nh::set_host_error("nh_test_get_chi2_params: the test is not a chi2test");
+        return NH_ERR_INVALID;
+    }
+    *out = test->data->chi2;
     return NH_OK;
 }
 

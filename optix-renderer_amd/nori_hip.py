@@ -299,6 +299,28 @@ _sig("nh_ttest_bsdf", _i32, _vp, C.POINTER(nh_bsdf), _fp, _f, C.c_uint64, _i32, 
 _sig("nh_test_run", _i32, C.c_int, C.c_char_p, C.c_uint64, C.POINTER(nh_test_result), _i32, _i32p)
 
 
+# ---- the chi^2 test (chi2test.cpp) ----
+class nh_chi2_params(C.Structure):
+    _fields_ = [("resolution", _i32), ("min_exp_frequency", _i32), ("test_count", _i32), ("sample_count", _i32)]
+
+
+class nh_chi2_result(C.Structure):
+    _fields_ = [("statistic", C.c_double), ("p_value", C.c_double), ("level", C.c_double), ("obs_sum", C.c_double),
+                ("exp_sum", C.c_double), ("wi", _f * 3), ("dof", _i32), ("pooled_cells", _i32), ("accepted", _i32),
+                ("kind", _i32), ("sample_count", _i32)]
+
+
+CHI2_MAX_CELLS = 8192  # NH_CHI2_MAX_CELLS
+CHI2_ACCEPTED, CHI2_REJECTED_P_VALUE, CHI2_REJECTED_ZERO_CELL, CHI2_REJECTED_DOF = 0, 1, 2, 3
+CHI2_KINDS = ("accepted", "p-value", "expected frequency 0", "degrees of freedom")
+_sig("nh_test_get_chi2_params", _i32, _vp, C.POINTER(nh_chi2_params))
+_sig("nh_chi2_histogram", _i32, _vp, C.POINTER(nh_bsdf), _fp, _fp, C.c_uint64, _i32, _i32, _i32, _dp)
+_sig("nh_chi2_expected", _i32, _vp, C.POINTER(nh_bsdf), _fp, _i32, _fp, _i32, _i32, _i32, _dp, _u32p)
+_sig("nh_chi2_test", _i32, _i32, _dp, _dp, _i32, C.c_double, C.c_double, _i32, _i32p, _dp, _dp, _i32p, _i32p, _i32p)
+_sig("nh_chi2_run", _i32, C.c_int, C.c_char_p, C.POINTER(nh_chi2_result), _i32, _i32p)
+_sig("nh_chi2_run_tables", _i32, C.c_int, C.c_char_p, C.POINTER(nh_chi2_result), _i32, _i32p, _dp)
+
+
 # ---- the photon mapper (photonmapper.cpp) ----
 INTEGRATOR_PHOTONMAPPER = 9
 EMITTER_QUERY_SAMPLE_PHOTON, EMITTER_QUERY_PHOTON_STRIDE = 3, 12
@@ -550,6 +572,14 @@ class Test:
             b = nh_bsdf()
             C.memmove(C.byref(b), C.byref(d.bsdfs[i]), C.sizeof(nh_bsdf))
             self.bsdfs.append(b)
+        # ChiSquareTest's own properties (nh_test_get_chi2_params; None on a ttest). sample_count stays the file's
+        # value (-1: automatic); chi2_sample_count is the resolved one
+        self.resolution = self.min_exp_frequency = self.test_count = self.chi2_sample_count = None
+        if d.type == TEST_CHI2TEST:
+            cp = nh_chi2_params()
+            _host_check(_lib.nh_test_get_chi2_params(h, C.byref(cp)), "test_get_chi2_params")
+            self.resolution, self.min_exp_frequency = int(cp.resolution), int(cp.min_exp_frequency)
+            self.test_count, self.chi2_sample_count = int(cp.test_count), int(cp.sample_count)
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -563,6 +593,50 @@ def students_t_test(mean: float, variance: float, reference: float, n: int, alph
     _host_check(_lib.nh_students_t_test(mean, variance, reference, n, alpha, num_tests, C.byref(ok), C.byref(p)),
                 "students_t_test")
     return bool(ok.value), p.value
+
+
+def chi2_test(obs, exp, sample_count: int, min_exp_frequency: float, alpha: float, num_tests: int) -> dict:
+    """hypothesis::chi2_test (nh_chi2_test): accepted, p_value, statistic, dof, pooled_cells and kind (CHI2_*) at the
+    Sidak-corrected level. On CHI2_REJECTED_ZERO_CELL statistic is the offending cell's observed count."""
+    obs = np.ascontiguousarray(obs, dtype=np.float64).ravel()
+    exp = np.ascontiguousarray(exp, dtype=np.float64).ravel()
+    if len(obs) != len(exp):
+        raise ValueError("chi2_test: obs and exp differ in length")
+    ok, dof, pooled, kind = _i32(0), _i32(0), _i32(0), _i32(0)
+    p, stat = C.c_double(0.0), C.c_double(0.0)
+    _host_check(_lib.nh_chi2_test(len(obs), obs.ctypes.data_as(_dp), exp.ctypes.data_as(_dp), sample_count,
+                                  min_exp_frequency, alpha, num_tests, C.byref(ok), C.byref(p), C.byref(stat),
+                                  C.byref(dof), C.byref(pooled), C.byref(kind)), "chi2_test")
+    return {"accepted": bool(ok.value), "p_value": p.value, "statistic": stat.value, "dof": dof.value,
+            "pooled_cells": pooled.value, "kind": kind.value}
+
+
+def run_chi2_tests(path: str, device: int = 0, tables: bool = True) -> list:
+    """ChiSquareTest::execute on the HIP path (nh_chi2_run): one dict per test of the file (<bsdf> x testCount) -- wi,
+    statistic, dof, pooled_cells, p_value, level, accepted, kind (CHI2_*), sample_count, obs_sum, exp_sum and, with
+    tables, obs and exp (cells float64 each, cell = cosThetaBin * 2 resolution + phiBin)."""
+    global _hip_used
+    _hip_used = True
+    t = Test(path)
+    if t.type != "chi2test":
+        cap, cells = 1, 1  # (nh_chi2_run refuses the file itself)
+    else:
+        cap = max(1, len(t.bsdfs) * max(t.test_count, 0))
+        cells = max(1, min(2 * t.resolution * t.resolution, CHI2_MAX_CELLS))
+    n = _i32(0)
+    res = (nh_chi2_result * cap)()
+    tab = np.zeros((cap, 2, cells), np.float64) if tables else None
+    _host_check(_lib.nh_chi2_run_tables(device, path.encode(), res, cap, C.byref(n),
+                                        None if tab is None else tab.ctypes.data_as(_dp)), f"run_chi2_tests {path}")
+    out = []
+    for i, r in enumerate(res[:n.value]):
+        d = {"wi": np.array(r.wi[:], np.float32), "statistic": r.statistic, "dof": r.dof,
+             "pooled_cells": r.pooled_cells, "p_value": r.p_value, "level": r.level, "accepted": bool(r.accepted),
+             "kind": r.kind, "sample_count": r.sample_count, "obs_sum": r.obs_sum, "exp_sum": r.exp_sum}
+        if tables:
+            d["obs"], d["exp"] = tab[i, 0].copy(), tab[i, 1].copy()
+        out.append(d)
+    return out
 
 
 def run_tests(path: str, seed: int = 0, device: int = 0) -> list:
@@ -908,6 +982,37 @@ class Context:
         self._check(_lib.nh_ttest_bsdf(self._h, C.byref(bsdf), None if alb is None else _fptr(alb), angle_deg, first_draw,
                                        n, C.byref(m), C.byref(v), None if lum is None else _fptr(lum)), "ttest_bsdf")
         return (m.value, v.value, lum) if luminance else (m.value, v.value)
+
+    def chi2_histogram(self, bsdf: nh_bsdf, wi, n: int, res_theta: int, res_phi: int, first_draw: int = 0,
+                       albedo=None) -> np.ndarray:
+        """nh_chi2_histogram: ChiSquareTest's contingency table of n samples of bsdf_sample at incident direction wi
+        (the BSDF's frame): sample k takes draws first_draw + 2k, + 2k + 1 of the default-state pcg32. (res_theta *
+        res_phi,) float64 of whole counts, the same bits on every run."""
+        w = np.ascontiguousarray(wi, dtype=np.float32).reshape(3)
+        alb = None if albedo is None else np.ascontiguousarray(albedo, dtype=np.float32).reshape(3)
+        obs = np.zeros(max(res_theta, 0) * max(res_phi, 0), np.float64)
+        self._check(_lib.nh_chi2_histogram(self._h, C.byref(bsdf), None if alb is None else _fptr(alb), _fptr(w),
+                                           first_draw, n, res_theta, res_phi, obs.ctypes.data_as(_dp)), "chi2_histogram")
+        return obs
+
+    def chi2_expected(self, bsdf: nh_bsdf, wi, res_theta: int, res_phi: int, sample_count: int, albedo=None,
+                      evals: bool = False):
+        """nh_chi2_expected: ChiSquareTest's expected frequencies for the incident directions wi ((m, 3), or (3,)) by
+        adaptiveSimpson2D of the device's bsdf_pdf over every cell, times sample_count. (m, cells) float64 ((cells,)
+        for one direction); with evals=True also the pdf evaluations per cell (uint32) as a second element."""
+        w = np.ascontiguousarray(wi, dtype=np.float32)
+        single = w.ndim == 1
+        w = np.ascontiguousarray(w.reshape(-1, 3))
+        alb = None if albedo is None else np.ascontiguousarray(albedo, dtype=np.float32).reshape(3)
+        cells = max(res_theta, 0) * max(res_phi, 0)
+        exp = np.zeros((len(w), cells), np.float64)
+        ev = np.zeros((len(w), cells), np.uint32) if evals else None
+        self._check(_lib.nh_chi2_expected(self._h, C.byref(bsdf), None if alb is None else _fptr(alb), len(w), _fptr(w),
+                                          res_theta, res_phi, sample_count, exp.ctypes.data_as(_dp),
+                                          None if ev is None else ev.ctypes.data_as(_u32p)), "chi2_expected")
+        if single:
+            exp, ev = exp[0], (None if ev is None else ev[0])
+        return (exp, ev) if evals else exp
 
     def trace(self, o: np.ndarray, d: np.ndarray, mint: np.ndarray, maxt: np.ndarray, any_hit=False,
               traversal: int = TRAVERSAL_REFERENCE) -> dict:
