@@ -22,10 +22,11 @@ HIP_FLAGS  := -std=c++17 -O3 -fPIC --offload-arch=$(ARCH) $(FP_FLAGS) \
 
 HOST_SRC := $(PKG)/host/xml_lite.cpp $(PKG)/host/scene_loader.cpp $(PKG)/host/bvh_build.cpp $(PKG)/host/image_io.cpp \
             $(PKG)/host/png_decode.cpp $(PKG)/host/hdr_decode.cpp $(PKG)/host/gpu_layout.cpp $(PKG)/host/ttest.cpp \
-            $(PKG)/host/photon_host.cpp $(PKG)/host/primary_masks.cpp $(PKG)/host/shadow_masks.cpp $(PKG)/host/chi2test.cpp
+            $(PKG)/host/photon_host.cpp $(PKG)/host/primary_masks.cpp $(PKG)/host/shadow_masks.cpp $(PKG)/host/chi2test.cpp \
+            $(PKG)/host/warptest.cpp
 HIP_SRC  := $(PKG)/csrc/nh_kernels.hip $(PKG)/csrc/nh_denoise.hip $(PKG)/csrc/nh_splat.hip $(PKG)/csrc/nh_api.hip \
             $(PKG)/csrc/nh_upload.hip $(PKG)/csrc/nh_pipeline.hip $(PKG)/csrc/nh_adaptive_api.hip $(PKG)/csrc/nh_query_api.hip \
-            $(PKG)/csrc/nh_photon_api.hip $(PKG)/csrc/nh_av.hip $(PKG)/csrc/nh_chi2_api.hip
+            $(PKG)/csrc/nh_photon_api.hip $(PKG)/csrc/nh_av.hip $(PKG)/csrc/nh_chi2_api.hip $(PKG)/csrc/nh_warp_api.hip
 HOST_OBJ := $(patsubst $(PKG)/host/%.cpp,$(OBJDIR)/host_%.o,$(HOST_SRC))
 # nh_wavefront.hip is compiled as five translation units (-DNH_WF_PART=k, each instantiating its own kernels) so
 # its kernels build in parallel
@@ -39,13 +40,14 @@ HIP_OBJ  := $(patsubst $(PKG)/csrc/%.hip,$(OBJDIR)/hip_%.o,$(HIP_SRC)) \
 # part 4 (the diffuse area-light instantiations) have no variant, and parts 1 and 2 leave their other kernels out.
 # nh_volume.hip (the volumetric path tracers and the medium query) is built this way only: one copy, with every BSDF
 # and emitter type. So are nh_adaptive.hip (the adaptive sampler's kernels) and nh_query.hip (the radiance query and the
-# t-test estimators), nh_photon.hip (the photon mapper's passes) and nh_chi2.hip (the chi^2 test's histogram and
-# expected-frequency kernels). The integrators themselves are device function templates in headers
-# (nh_integrators.h, nh_volume.h), shared by these units.
+# t-test estimators), nh_photon.hip (the photon mapper's passes), nh_chi2.hip (the chi^2 test's histogram and
+# expected-frequency kernels) and nh_warp.hip (the warp test's histogram, expected-frequency and query kernels). The
+# integrators themselves are device function templates in headers (nh_integrators.h, nh_volume.h), shared by these
+# units.
 DZ_PARTS := 1 2
 HIP_OBJ  += $(OBJDIR)/hipdz_nh_kernels.o $(OBJDIR)/hipdz_nh_disney.o $(OBJDIR)/hipdz_nh_emitter_query.o \
             $(OBJDIR)/hipdz_nh_volume.o $(OBJDIR)/hipdz_nh_adaptive.o $(OBJDIR)/hipdz_nh_query.o \
-            $(OBJDIR)/hipdz_nh_photon.o $(OBJDIR)/hipdz_nh_chi2.o \
+            $(OBJDIR)/hipdz_nh_photon.o $(OBJDIR)/hipdz_nh_chi2.o $(OBJDIR)/hipdz_nh_warp.o \
             $(foreach k,$(DZ_PARTS),$(OBJDIR)/hipdz_nh_wavefront_p$(k).o)
 HIP_DEPS := $(wildcard $(PKG)/csrc/*.h) $(PKG)/host/gpu_layout.h include/nori_hip.h
 # The wavefront kernels build without LLVM's machine-level LICM: it hoists loop invariants out of the traversal, bounce
@@ -61,6 +63,7 @@ CLI      := $(LIBDIR)/nori_hip
 
 RCPCHECK := tools/bin/rcp_exhaustive
 VALUBENCH := tools/bin/valu_issue
+WARPRATE := tools/bin/warp_rate
 
 MANUAL   := tests/c/bin/manual_scene
 LAYOUTCHECK := tests/c/bin/gpu_layout_check
@@ -68,7 +71,7 @@ DISPATCHCHECK := tests/c/bin/dispatch_check
 FLATCHECK := tests/c/bin/flat_combine_check
 SIMPSONCHECK := tests/c/bin/simpson_check
 
-all: $(LIB) $(HOSTLIB) $(ORACLE) $(CLI) $(RCPCHECK) $(VALUBENCH) $(MANUAL) $(LAYOUTCHECK) $(DISPATCHCHECK) $(FLATCHECK) $(SIMPSONCHECK)
+all: $(LIB) $(HOSTLIB) $(ORACLE) $(CLI) $(RCPCHECK) $(VALUBENCH) $(WARPRATE) $(MANUAL) $(LAYOUTCHECK) $(DISPATCHCHECK) $(FLATCHECK) $(SIMPSONCHECK)
 
 # C test: a scene description filled field by field (no XML loader), rendered through the C-ABI and
 # compared with the oracle (run by tests/test_gpu_parity.py)
@@ -110,6 +113,11 @@ $(RCPCHECK): tools/rcp_exhaustive.hip $(HIP_DEPS)
 $(VALUBENCH): tools/valu_issue.hip
 	@mkdir -p tools/bin
 	$(HIPCC) -std=c++17 -O3 --offload-arch=$(ARCH) -o $@ $<
+
+# the warp test's first measurement (profiles/warp_rate.txt): nh_warp_run's wall time and the histogram kernel's rate
+$(WARPRATE): tools/warp_rate.hip $(LIB) $(HIP_DEPS)
+	@mkdir -p tools/bin
+	$(HIPCC) $(HIP_FLAGS) -o $@ $< -L$(LIBDIR) -lnori_hip -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
 
 # the GPU layout code was part of the -O3 C-ABI unit before it moved to host/: at -O2 a 10M-triangle upload took 5 %
 # longer (profiles/api_split_bench.txt). Contraction stays off.

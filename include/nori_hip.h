@@ -824,6 +824,62 @@ int nh_chi2_run(int device, const char *path, nh_chi2_result *results, int32_t c
 int nh_chi2_run_tables(int device, const char *path, nh_chi2_result *results, int32_t cap, int32_t *n_results,
                        double *tables);
 
+/* ---- the reference's warp test (src/utils/warptest.cpp, runTest) ------------------------ */
+
+/* WarpTest::WarpType (warptest.cpp:67-81), in its order. NH_WARP_SCHLICK exists only to be refused by name
+ * (NH_ERR_UNSUPPORTED): squareToSchlick leaves [-1, 1], and the reference then bins a NaN through an (int) cast, which
+ * is undefined -- the reason the loader gives for the phase function. */
+enum { NH_WARP_NONE = 0, NH_WARP_DISK, NH_WARP_UNIFORM_SPHERE, NH_WARP_UNIFORM_SPHERE_VOL, NH_WARP_UNIFORM_SPHERE_CAP,
+       NH_WARP_UNIFORM_HEMISPHERE, NH_WARP_COSINE_HEMISPHERE, NH_WARP_BECKMANN, NH_WARP_HENYEY_GREENSTEIN,
+       NH_WARP_SCHLICK, NH_WARP_MICROFACET_BRDF, NH_WARP_ISO_PHASE, NH_WARP_ANISO_PHASE };
+/* mapParameter (warptest.cpp:88-100) in fp32 as written: the parameter slider's value in [0, 1] becomes alpha =
+ * exp(log(0.05) (1 - s) + log(1) s) for Beckmann and the microfacet BRDF, g = 2 s - 1 for Henyey-Greenstein and the
+ * anisotropic phase function, and stays as it is for the rest (the sphere cap takes it as cosThetaMax). Host only. */
+int nh_warp_map_parameter(int32_t type, float slider, float *value);
+/* The incident direction of the BRDF and the phase functions from the angle slider (warptest.cpp:183-184):
+ * (sin a, 0, max(cos a, 1e-4)).normalized() with a = M_PI (s - 0.5). Host only. */
+int nh_warp_wi(float angle_slider, float wi[3]);
+/* Every entry point below takes the type, the mapped parameter (finite) and wi (3 floats; read for
+ * NH_WARP_MICROFACET_BRDF only, may be NULL otherwise). The microfacet BRDF is microfacet.cpp's with alpha =
+ * parameter, kd = 0 (so ks = 1) and its default intIOR / extIOR, run through the bsdf_sample / bsdf_eval / bsdf_pdf
+ * device functions; the phases through phase_sample / phase_pdf. None needs an uploaded scene.
+ *
+ * nh_warp_query, one lane per query:
+ *   NH_WARP_QUERY_SAMPLE  in: 3n floats, the Point3f sample (only the sphere volume reads z). out: 4n floats, the
+ *                         warped point and warpPoint's weight (warptest.cpp:102-131): 1, or for the microfacet BRDF
+ *                         value == 0 ? 0 : eval[0]
+ *   NH_WARP_QUERY_PDF     in: 3n floats, the point (None and Disk use x, y only). out: n floats, the matching *Pdf in
+ *                         fp32; the BRDF's pdf in the solid-angle measure */
+enum { NH_WARP_QUERY_SAMPLE = 0, NH_WARP_QUERY_PDF = 1 };
+int nh_warp_query(nh_ctx *ctx, int32_t type, float parameter, const float *wi, int32_t mode, int32_t n,
+                  const float *in, float *out);
+/* generatePoints(Independent) and runTest's binning loop (warptest.cpp:146-168, :457-479). Point k takes three
+ * consecutive draws of the default-state pcg32 from draw first_draw + 3k. Point3f(nextFloat(), nextFloat(),
+ * nextFloat()) leaves the order of its arguments to the compiler: draw_order NH_LENS_DRAWS_RTL (g++: x = draw 3k + 2,
+ * z = draw 3k) or NH_LENS_DRAWS_LTR (x = draw 3k). A point of weight 0 is skipped. A point with a NaN coordinate is not
+ * counted either -- the reference's (int) cast is undefined there -- but tallied in *nan_points (may be NULL). The rest
+ * are binned in fp32 as written: None by (x, y), Disk by 0.5 p + 0.5, everything else by atan2(y, x) * INV_TWOPI
+ * wrapped into [0, 1) and 0.5 z + 0.5 of the point as it is (sphere-volume points are not normalized); every bin is
+ * min(res - 1, max(0, floor(v res))). obs: yres * xres doubles, row ybin, whole counts, the same bits on every run.
+ * 1 <= n <= INT32_MAX (NH_ERR_INVALID); xres, yres >= 1 and xres * yres <= NH_CHI2_MAX_CELLS (NH_ERR_UNSUPPORTED). */
+int nh_warp_histogram(nh_ctx *ctx, int32_t type, float parameter, const float *wi, uint64_t first_draw,
+                      int32_t draw_order, int32_t n, int32_t xres, int32_t yres, double *obs, uint32_t *nan_points);
+/* runTest's expected frequencies (warptest.cpp:481-551): per cell hypothesis::adaptiveSimpson2D (eps 1e-6, depth 6;
+ * csrc/nh_simpson.h) of the integrand as written -- yStart = y / (double)yres, yEnd = (y + 1 - Epsilon) / (double)yres,
+ * likewise for x, the direction built in fp64 with the reference's float M_PI and narrowed to fp32, the pdf in fp32 --
+ * times sample_count x 1 (None), 4 (Disk) or 4 * M_PI. exp: yres * xres doubles; evals (may be NULL): the pdf
+ * evaluations each cell took. A negative cell returns NH_ERR_INVALID with the reference's message "The Pdf() function
+ * returned negative values!". Resolution limits as nh_warp_histogram's. */
+int nh_warp_expected(nh_ctx *ctx, int32_t type, float parameter, const float *wi, int32_t xres, int32_t yres,
+                     int32_t sample_count, double *exp, uint32_t *evals);
+/* runTest (warptest.cpp:439-562) on device `device`: nh_warp_map_parameter, nh_warp_wi, the two tables from draw 0,
+ * then nh_chi2_test with minExpFrequency 5, significance level 0.01 and one test. xres = yres = sample_count = 0
+ * selects the reference's own values: 51 x 51 cells, xres doubled except for None and Disk, 1000 samples per cell.
+ * result->wi is zero where the type has no incident direction. tables (may be NULL): yres * xres observed then as
+ * many expected frequencies. Errors through nh_host_last_error. */
+int nh_warp_run(int device, int32_t type, float parameter_slider, float angle_slider, int32_t draw_order, int32_t xres,
+                int32_t yres, int32_t sample_count, nh_chi2_result *result, double *tables);
+
 /* ---- the photon mapper (src/integrators/photonmapper.cpp) ------------------------------- */
 
 /* Photon path k draws from its own stream path_rng(seed, NH_PHOTON_STREAM, k): no pixel index reaches 2^32. */

@@ -423,6 +423,57 @@ NHD F3 uniform_sphere(float sx, float sy) {  // warp.cpp:74-82
     w.y = r * ss;
     return normalized(w);
 }
+// The warps and densities below are called by the warp test alone (nh_warp.hip): the render
+// kernels carry the ones they need inline in their emitter, camera and BSDF code.
+NHD float uniform_square_pdf(float x, float y) {  // warp.cpp:43-46
+    return (x >= 0 && y >= 0 && x <= 1 && y <= 1) ? 1.0f : 0.0f;
+}
+NHD void uniform_disk(float sx, float sy, float &x, float &y) {  // warp.cpp:48-52
+    float rho = f_sqrt(sx);
+    float theta = sy * 2.0f * kPi;
+    float st, ct;
+    f_sincos(theta, st, ct);
+    x = rho * ct;
+    y = rho * st;
+}
+NHD float uniform_disk_pdf(float x, float y) { return (x * x + y * y <= 1.0f) ? 1.0f / kPi : 0.0f; }  // warp.cpp:54-56
+NHD F3 uniform_sphere_cap(float sx, float sy, float cos_max) {  // warp.cpp:58-66
+    float z = sx * (1.0f - cos_max) + cos_max;
+    float r = f_sqrt(1.0f - z * z);
+    float theta = sy * 2.0f * kPi;
+    float st, ct;
+    f_sincos(theta, st, ct);
+    return f3(r * ct, r * st, z);
+}
+// warp.cpp:68-72, as written: zero for a unit vector at or below the cap's rim, the cap's density everywhere else
+NHD float uniform_sphere_cap_pdf(F3 v, float cos_max) {
+    return (fabsf(dot(v, v) - 1.0f) < kEps && v.z <= cos_max) ? 0.0f : 1.0f / (2.0f * kPi * (1.0f - cos_max));
+}
+NHD float uniform_sphere_pdf(F3 v) { return (fabsf(dot(v, v) - 1.0f) < kEps) ? 0.25f / kPi : 0.0f; }  // warp.cpp:84-86
+NHD float f_cbrt(float x) { return (float)cbrt((double)x); }  // std::cbrt(float): fp64, rounded once
+NHD F3 uniform_sphere_volume(float sx, float sy, float sz) {  // warp.cpp:88-92
+    const float r = f_cbrt(sz);
+    return scl(r, uniform_sphere(sx, sy));
+}
+NHD float uniform_sphere_volume_pdf() { return 4.f / 3.f * kPi; }  // warp.cpp:94-97, as written (not a density)
+NHD F3 uniform_hemisphere(float sx, float sy) {  // warp.cpp:99-103
+    F3 w = uniform_sphere(sx, sy);
+    w.z = fabsf(w.z);
+    return w;
+}
+NHD float uniform_hemisphere_pdf(F3 v) {  // warp.cpp:105-109
+    return (fabsf(dot(v, v) - 1) < kEps && v.z > 0) ? 2.0f * uniform_sphere_pdf(v) : 0.0f;
+}
+NHD float cosine_hemisphere_pdf(F3 v) {  // warp.cpp:124-129
+    return (fabsf(dot(v, v) - 1) < kEps && v.z > 0) ? v.z / kPi : 0.0f;
+}
+NHD float beckmann_pdf(F3 m, float alpha) {  // warp.cpp:152-160 (the BSDF's own D is beckmann_d, microfacet.cpp)
+    float c_t = m.z;
+    float r = f_sqrt(m.x * m.x + m.y * m.y);
+    float tantheta = r / m.z;
+    if (fabsf(dot(m, m) - 1) > kEps || m.z < 0) return 0.f;
+    return f_exp(-tantheta * tantheta / alpha / alpha) / (kPi * alpha * alpha * c_t * c_t * c_t);
+}
 
 // ---- BSDFs (src/bsdf) ---------------------------------------------------------------
 NHD float tan_theta(F3 v) {

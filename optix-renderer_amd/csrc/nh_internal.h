@@ -519,3 +519,47 @@ void launch_chi2_histogram(const Chi2Hist &h, hipStream_t st);
 void launch_chi2_expected(const Chi2Expected &e, hipStream_t st);
 }  // namespace nh
 }  // namespace nh_disney
+
+// ---- the warp test (warptest.cpp's runTest; nh_warp.hip, driven by nh_warp_api.hip) ----
+// What every warp kernel knows of the test: the NH_WARP_* type, the mapped parameter, and for the microfacet BRDF the
+// incident direction and the BSDF record (alpha = parameter, kd = 0)
+struct WarpSpec {
+    int type;
+    float parameter;
+    float wi[3];
+    nhd::DBsdf bsdf;
+};
+// generatePoints + the binning loop: lane l owns points [l run, (l + 1) run) of the n, point j at draws first_draw + 3j
+// .. + 3j + 2 of the default-state pcg32 (rtl: x is the last of the three). counts: yres * xres uint32 and *nan_points,
+// zeroed by the caller. The block size, run length and grid cap are the chi^2 histogram's (kChi2Block, ..)
+struct WarpHist {
+    WarpSpec w;
+    uint64_t first_draw;
+    int n, run;
+    int xres, yres;
+    int rtl;
+    int sub_tables;
+    uint32_t *counts;
+    uint32_t *nan_points;
+};
+struct WarpExpected {
+    WarpSpec w;
+    int xres, yres;
+    double scale;  // sample_count x 1, 4 or 4 * M_PI
+    double *exp;
+    uint32_t *evals;  // may be null
+};
+// one lane per query: mode NH_WARP_QUERY_SAMPLE (in 3n, out 4n) or NH_WARP_QUERY_PDF (in 3n, out n)
+struct WarpQuery {
+    WarpSpec w;
+    int mode, n;
+    const float *in;
+    float *out;
+};
+namespace nh_disney {
+namespace nh {
+void launch_warp_histogram(const WarpHist &h, hipStream_t st);
+void launch_warp_expected(const WarpExpected &e, hipStream_t st);
+void launch_warp_query(const WarpQuery &q, hipStream_t st);
+}  // namespace nh
+}  // namespace nh_disney

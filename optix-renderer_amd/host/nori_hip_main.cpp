@@ -56,6 +56,26 @@ static int run_tests(const std::string &path, const nh_test *test, int device, u
     return passed == n ? 0 : 1;
 }
 
+// hypothesis::chi2_test's message (hypothesis.h:163-234) for one verdict; true when the null hypothesis was accepted
+static bool report_chi2(const nh_chi2_result &r, double min_exp_frequency) {
+    if (r.kind == NH_CHI2_REJECTED_ZERO_CELL) {
+        std::printf("Encountered %g samples in a cell with expected frequency 0. Rejecting the null hypothesis!\n\n",
+                    r.statistic);
+        return false;
+    }
+    if (r.pooled_cells > 0)
+        std::printf("Pooled %d to ensure sufficiently high expected cell frequencies (>%g)\n", r.pooled_cells,
+                    min_exp_frequency);
+    if (r.kind == NH_CHI2_REJECTED_DOF) {
+        std::printf("The number of degrees of freedom (%d) is too low!\n\n", r.dof);
+        return false;
+    }
+    std::printf("Chi^2 statistic = %g (d.o.f. = %d)\n", r.statistic, r.dof);
+    std::printf("%s the null hypothesis (p-value = %g, significance level = %g)\n\n",
+                r.accepted ? "Accepted" : "***** Rejected *****", r.p_value, r.level);
+    return r.accepted != 0;
+}
+
 // ChiSquareTest::execute's report (chi2test.cpp:147-233, hypothesis.h:163-234) for a <test type="chi2test"> file run
 // on the HIP path (nh_chi2_run); 0 only if every test passed. The chi2test_%i.m dumps are not written.
 static int run_chi2_tests(const std::string &path, const nh_test *test, int device) {
@@ -75,32 +95,54 @@ static int run_chi2_tests(const std::string &path, const nh_test *test, int devi
         std::printf("Accumulating %d samples into a %dx%d contingency table .. done.\n", r.sample_count, cp.resolution,
                     2 * cp.resolution);
         std::printf("Integrating expected frequencies .. done.\n");
-        if (r.kind == NH_CHI2_REJECTED_ZERO_CELL) {
-            std::printf("Encountered %g samples in a cell with expected frequency 0. Rejecting the null hypothesis!\n\n",
-                        r.statistic);
-            continue;
-        }
-        if (r.pooled_cells > 0)
-            std::printf("Pooled %d to ensure sufficiently high expected cell frequencies (>%g)\n", r.pooled_cells,
-                        (double)cp.min_exp_frequency);
-        if (r.kind == NH_CHI2_REJECTED_DOF) {
-            std::printf("The number of degrees of freedom (%d) is too low!\n\n", r.dof);
-            continue;
-        }
-        std::printf("Chi^2 statistic = %g (d.o.f. = %d)\n", r.statistic, r.dof);
-        std::printf("%s the null hypothesis (p-value = %g, significance level = %g)\n\n",
-                    r.accepted ? "Accepted" : "***** Rejected *****", r.p_value, r.level);
-        passed += r.accepted ? 1 : 0;
+        passed += report_chi2(r, (double)cp.min_exp_frequency) ? 1 : 0;
     }
     std::printf("Passed %d/%d tests.\n", passed, (int)n);
     return passed == n ? 0 : 1;
 }
 
+// WarpTest::runTest (warptest.cpp:439-562) on the HIP path (nh_warp_run), headless: the verdict text of
+// hypothesis::chi2_test, which the GUI shows in its message box; 0 on accept, 1 on reject
+static const char *const kWarpNames[] = {"none", "disk", "sphere", "spherevol", "spherecap", "hemisphere", "cosinehemisphere",
+                                         "beckmann", "henyeygreenstein", "schlick", "microfacet", "isophase", "anisophase"};
+static int run_warp_test(int argc, char **argv) {
+    if (argc < 3) return die("--warptest", "needs a warp name");
+    int type = -1, device = 0, xres = 0, yres = 0, samples = 0, order = NH_LENS_DRAWS_RTL;
+    for (int t = 0; t < (int)(sizeof(kWarpNames) / sizeof(kWarpNames[0])); ++t)
+        if (std::strcmp(argv[2], kWarpNames[t]) == 0) type = t;
+    if (type < 0) return die("--warptest: unknown warp", argv[2]);
+    float param = 0.5f, angle = 0.5f;
+    for (int i = 3; i < argc; ++i) {
+        std::string a = argv[i];
+        auto next = [&]() { return i + 1 < argc ? argv[++i] : (char *)"0"; };
+        if (a == "--param") param = (float)std::atof(next());
+        else if (a == "--angle") angle = (float)std::atof(next());
+        else if (a == "--res") {
+            xres = std::atoi(next());
+            yres = std::atoi(next());
+        } else if (a == "--samples") samples = std::atoi(next());
+        else if (a == "--ltr") order = NH_LENS_DRAWS_LTR;
+        else if (a == "--device") device = std::atoi(next());
+        else return die("argument", a.c_str());
+    }
+    if ((xres || yres) && !samples) samples = 1000 * xres * yres;  // runTest's own density
+    nh_chi2_result r;
+    if (nh_warp_run(device, type, param, angle, order, xres, yres, samples, &r, nullptr))
+        return die("warptest", nh_host_last_error());
+    float value = 0.f;
+    nh_warp_map_parameter(type, param, &value);
+    std::printf("Testing warp: %s (parameter = %g, wi = [%g, %g, %g])\n", kWarpNames[type], value, r.wi[0], r.wi[1], r.wi[2]);
+    std::printf("Accumulated %d points .. done.\nIntegrating expected frequencies .. done.\n", r.sample_count);
+    return report_chi2(r, 5.0) ? 0 : 1;
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) {
-        std::fprintf(stderr, "usage: nori_hip scene.xml [--spp N] [--width W --height H] [--device D] [--ordered] [--pfm out] [--png] [--seed S]\n");
+        std::fprintf(stderr, "usage: nori_hip scene.xml [--spp N] [--width W --height H] [--device D] [--ordered] [--pfm out] [--png] [--seed S]\n"
+                             "       nori_hip --warptest <name> [--param s] [--angle s] [--res X Y] [--samples N] [--ltr] [--device D]\n");
         return 1;
     }
+    if (std::strcmp(argv[1], "--warptest") == 0) return run_warp_test(argc, argv);
     std::string scene_path = argv[1], pfm;
     bool png = false;
     int spp = 0, w = 0, h = 0, device = 0, traversal = NH_TRAVERSAL_REFERENCE;

@@ -320,6 +320,22 @@ _sig("nh_chi2_test", _i32, _i32, _dp, _dp, _i32, C.c_double, C.c_double, _i32, _
 _sig("nh_chi2_run", _i32, C.c_int, C.c_char_p, C.POINTER(nh_chi2_result), _i32, _i32p)
 _sig("nh_chi2_run_tables", _i32, C.c_int, C.c_char_p, C.POINTER(nh_chi2_result), _i32, _i32p, _dp)
 
+# ---- the warp test (warptest.cpp's runTest) ----
+(WARP_NONE, WARP_DISK, WARP_UNIFORM_SPHERE, WARP_UNIFORM_SPHERE_VOL, WARP_UNIFORM_SPHERE_CAP, WARP_UNIFORM_HEMISPHERE,
+ WARP_COSINE_HEMISPHERE, WARP_BECKMANN, WARP_HENYEY_GREENSTEIN, WARP_SCHLICK, WARP_MICROFACET_BRDF, WARP_ISO_PHASE,
+ WARP_ANISO_PHASE) = range(13)
+# the names the CLI's --warptest takes, by type
+WARP_NAMES = ("none", "disk", "sphere", "spherevol", "spherecap", "hemisphere", "cosinehemisphere", "beckmann",
+              "henyeygreenstein", "schlick", "microfacet", "isophase", "anisophase")
+WARP_SUPPORTED = tuple(t for t in range(13) if t != WARP_SCHLICK)
+WARP_QUERY_SAMPLE, WARP_QUERY_PDF = 0, 1
+_sig("nh_warp_map_parameter", _i32, _i32, _f, _fp)
+_sig("nh_warp_wi", _i32, _f, _fp)
+_sig("nh_warp_query", _i32, _vp, _i32, _f, _fp, _i32, _i32, _fp, _fp)
+_sig("nh_warp_histogram", _i32, _vp, _i32, _f, _fp, C.c_uint64, _i32, _i32, _i32, _i32, _dp, _u32p)
+_sig("nh_warp_expected", _i32, _vp, _i32, _f, _fp, _i32, _i32, _i32, _dp, _u32p)
+_sig("nh_warp_run", _i32, C.c_int, _i32, _f, _f, _i32, _i32, _i32, _i32, C.POINTER(nh_chi2_result), _dp)
+
 
 # ---- the photon mapper (photonmapper.cpp) ----
 INTEGRATOR_PHOTONMAPPER = 9
@@ -637,6 +653,50 @@ def run_chi2_tests(path: str, device: int = 0, tables: bool = True) -> list:
             d["obs"], d["exp"] = tab[i, 0].copy(), tab[i, 1].copy()
         out.append(d)
     return out
+
+
+def warp_map_parameter(type: int, slider: float) -> float:
+    """mapParameter (warptest.cpp:88-100, nh_warp_map_parameter): the parameter slider's value as the warp takes it."""
+    v = _f(0.0)
+    _host_check(_lib.nh_warp_map_parameter(type, slider, C.byref(v)), "warp_map_parameter")
+    return float(v.value)
+
+
+def warp_wi(angle_slider: float) -> np.ndarray:
+    """The incident direction the angle slider stands for (warptest.cpp:183-184, nh_warp_wi)."""
+    wi = np.zeros(3, np.float32)
+    _host_check(_lib.nh_warp_wi(angle_slider, _fptr(wi)), "warp_wi")
+    return wi
+
+
+def warp_default_table(type: int):
+    """runTest's own (yres, xres, sample_count) (warptest.cpp:440-447)."""
+    yres, xres = 51, 51 if type in (WARP_NONE, WARP_DISK) else 102
+    return yres, xres, 1000 * yres * xres
+
+
+def run_warp_test(type: int, parameter_slider: float = 0.5, angle_slider: float = 0.5, draw_order: int = LENS_DRAWS_RTL,
+                  xres: int = 0, yres: int = 0, sample_count: int = 0, device: int = 0, tables: bool = True) -> dict:
+    """WarpTest::runTest on the HIP path (nh_warp_run): wi, statistic, dof, pooled_cells, p_value, level, accepted,
+    kind (CHI2_*), sample_count, obs_sum, exp_sum, xres, yres and, with tables, obs and exp (yres * xres float64 each,
+    cell = ybin * xres + xbin). xres = yres = sample_count = 0: the reference's own table (warp_default_table)."""
+    global _hip_used
+    _hip_used = True
+    if xres == 0 and yres == 0 and sample_count == 0:
+        ty, tx, _ = warp_default_table(type)
+    else:
+        ty, tx = yres, xres
+    cells = max(1, min(max(tx, 0) * max(ty, 0), CHI2_MAX_CELLS))
+    r = nh_chi2_result()
+    tab = np.zeros((2, cells), np.float64) if tables else None
+    _host_check(_lib.nh_warp_run(device, type, parameter_slider, angle_slider, draw_order, xres, yres, sample_count,
+                                 C.byref(r), None if tab is None else tab.ctypes.data_as(_dp)), "run_warp_test")
+    d = {"wi": np.array(r.wi[:], np.float32), "statistic": r.statistic, "dof": r.dof, "pooled_cells": r.pooled_cells,
+         "p_value": r.p_value, "level": r.level, "accepted": bool(r.accepted), "kind": r.kind,
+         "sample_count": r.sample_count, "obs_sum": r.obs_sum, "exp_sum": r.exp_sum, "xres": tx, "yres": ty}
+    if tables:
+        d["obs"], d["exp"] = tab[0].copy(), tab[1].copy()
+    return d
 
 
 def run_tests(path: str, seed: int = 0, device: int = 0) -> list:
@@ -1012,6 +1072,42 @@ class Context:
                                           None if ev is None else ev.ctypes.data_as(_u32p)), "chi2_expected")
         if single:
             exp, ev = exp[0], (None if ev is None else ev[0])
+        return (exp, ev) if evals else exp
+
+    @staticmethod
+    def _warp_wi(wi):
+        return None if wi is None else _fptr(np.ascontiguousarray(wi, dtype=np.float32).reshape(3))
+
+    def warp_query(self, type: int, parameter: float, mode: int, inp, wi=None) -> np.ndarray:
+        """nh_warp_query: warpPoint (WARP_QUERY_SAMPLE: inp (n, 3) samples -> (n, 4) point and weight) or the matching
+        pdf (WARP_QUERY_PDF: inp (n, 3) points -> (n,)) of warp `type` at the mapped parameter; wi for the BRDF."""
+        inp = np.ascontiguousarray(inp, dtype=np.float32).reshape(-1, 3)
+        out = np.zeros((len(inp), 4) if mode == WARP_QUERY_SAMPLE else (len(inp),), np.float32)
+        self._check(_lib.nh_warp_query(self._h, type, parameter, self._warp_wi(wi), mode, len(inp), _fptr(inp),
+                                       _fptr(out)), "warp_query")
+        return out
+
+    def warp_histogram(self, type: int, parameter: float, n: int, xres: int, yres: int, first_draw: int = 0,
+                       draw_order: int = LENS_DRAWS_RTL, wi=None):
+        """nh_warp_histogram: (obs, nan_points) -- runTest's table of n points of the default-state pcg32 from draw
+        first_draw ((yres * xres,) float64 of whole counts, the same bits on every run) and the number of points left
+        out because a coordinate was NaN."""
+        obs = np.zeros(max(xres, 0) * max(yres, 0), np.float64)
+        nan = _u32(0)
+        self._check(_lib.nh_warp_histogram(self._h, type, parameter, self._warp_wi(wi), first_draw, draw_order, n, xres,
+                                           yres, obs.ctypes.data_as(_dp), C.byref(nan)), "warp_histogram")
+        return obs, int(nan.value)
+
+    def warp_expected(self, type: int, parameter: float, xres: int, yres: int, sample_count: int, wi=None,
+                      evals: bool = False):
+        """nh_warp_expected: runTest's expected frequencies, (yres * xres,) float64; with evals=True also the pdf
+        evaluations per cell (uint32) as a second element."""
+        cells = max(xres, 0) * max(yres, 0)
+        exp = np.zeros(cells, np.float64)
+        ev = np.zeros(cells, np.uint32) if evals else None
+        self._check(_lib.nh_warp_expected(self._h, type, parameter, self._warp_wi(wi), xres, yres, sample_count,
+                                          exp.ctypes.data_as(_dp), None if ev is None else ev.ctypes.data_as(_u32p)),
+                    "warp_expected")
         return (exp, ev) if evals else exp
 
     def trace(self, o: np.ndarray, d: np.ndarray, mint: np.ndarray, maxt: np.ndarray, any_hit=False,
